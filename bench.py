@@ -14,7 +14,14 @@ fold k's W + traceback; measured slower, so the default is 1).  Every fold is co
 before the clock stops, and the barrier + wall clock around the K steps brackets finished GPU work.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 200] [--seed 5] [--params Turner04]
-                    [--distinct] [--shard]
+                    [--distinct] [--shard] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the in-step breakdown and the level roofline from the timed steps' own events).
+--dump-outputs DIR then writes what the last timed step returned to its caller (energy, structure,
+W and the 2-D matrices) as DIR/<name>.npy.  --full adds everything that takes work of its own: the
+instrumented fold (per-kernel-family times and their rooflines), the CPU baseline and the
+comparisons with the reference.
 
 Multi-GPU (one process per GPU):
   * launched by torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE set), or
@@ -98,6 +105,38 @@ def job_value(cells, steps, elapsed, world, shard):
     sequence per step over all ranks."""
     seqs_per_step = 1 if shard else world
     return seqs_per_step * steps * cells / elapsed
+
+
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64.  When all of them together would
+    pass DUMP_CAP_BYTES, every array larger than its equal share is cut to a fixed sample (sorted
+    indices drawn by numpy's default_rng(0), the same from run to run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrs.values()) > DUMP_CAP_BYTES:
+        share = DUMP_CAP_BYTES // (8 * len(arrs))
+        for k, v in arrs.items():
+            if v.size > share:
+                arrs[k] = v[np.sort(np.random.default_rng(0).choice(v.size, share, replace=False))]
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def mfe_outputs(wf):
+    """What a caller of the timed fold holds afterwards (ccj_amd.W_final): the MFE, the dot-bracket
+    string (one character code per base), the exterior W and the eight 2-D matrices in canonical
+    order (i = 1..n, j = i..n)."""
+    from ccj_amd import MAT2
+    n = wf.n
+    out = {"energy": [wf.energy], "structure": [ord(ch) for ch in wf.structure],
+           "W": [wf.W(j) for j in range(n + 1)]}
+    for m, name in enumerate(MAT2):
+        out["mat2_" + name] = [wf.get2(m, i, j) for i in range(1, n + 1) for j in range(i, n + 1)]
+    return out
 
 
 def share_comm_id(rank, dist, make_id):
@@ -246,16 +285,36 @@ def pf_bench(a, rank, world, dist, barrier, dev=0):
     elapsed = time.perf_counter() - t0
     barrier()
     elapsed = max_over_ranks(elapsed, dist)
-    # after the timed region: one fill with an event pair around every launch (per-family durations)
-    pf.set_timing(True)
-    pf.ccj_pf()
-    kms = pf.kernel_ms()
-    pf.set_timing(False)
-    work = pf.work_model()
+    if a.dump_outputs and rank == 0:
+        from ccj_amd import PF_MAT2
+        dump_outputs(a.dump_outputs, {"energy": [e], "W": pf.W(), **{"mat2_" + m: pf.get2(m) for m in PF_MAT2}})
+    kms = work = None
+    if a.full:
+        # after the timed region: one fill with an event pair around every launch (per-family durations)
+        pf.set_timing(True)
+        pf.ccj_pf()
+        kms = pf.kernel_ms()
+        pf.set_timing(False)
+        work = pf.work_model()
     pf.close()
     if rank != 0:
         return
     cells = num_cells(a.n)
+    out = {
+        "metric": PF_METRIC, "value": cells * world * a.steps / elapsed, "unit": "DP-cells/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f64+int32", "data": "synthetic",
+        "config": {"workload": f"CCJ partition function (W_final_pf::ccj_pf: fill of the 21 int32 4-D and 8 double "
+                               f"2-D matrices, W, energy; bit-identical to part_func.cc) of a {a.n}-nt random "
+                               f"ACGU RNA per GPU (seed {a.seed}+rank), rna_{a.params}, dangles 2; replicas",
+                   "n": a.n, "seed": a.seed, "params": a.params, "cells_per_fold": cells,
+                   "parallelism": f"replicas{world}"},
+        "sec_per_sequence": elapsed / a.steps, "nt_per_s": a.n * world * a.steps / elapsed,
+        "fill_ms": fill_ms / a.steps, "create_ms": create_ms, "energy": e,
+    }
+    if not a.full:
+        print(json.dumps(out), flush=True)
+        return
     nl = {"k_pf_iloop": max(a.n - 2, 1), "k_pf_level": max(a.n - 2, 1), "k_pf_pterm": max(a.n - 3, 1),
           "k_pf_ppush": max(a.n - 3, 1), "k_pf_diag": a.n}
 
@@ -276,21 +335,11 @@ def pf_bench(a, rank, world, dist, barrier, dev=0):
                 "kernel": k, "launches_per_fold": nl[k], "avg_launch_us": avg_s * 1e6,
                 "algorithmic_bytes_per_fold": work[k], "kernel_ms_per_fold": ms}
     dom = max(kms, key=kms.get)
-    out = {
-        "metric": PF_METRIC, "value": cells * world * a.steps / elapsed, "unit": "DP-cells/s", "n_gpus": world,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f64+int32", "data": "synthetic",
-        "config": {"workload": f"CCJ partition function (W_final_pf::ccj_pf: fill of the 21 int32 4-D and 8 double "
-                               f"2-D matrices, W, energy; bit-identical to part_func.cc) of a {a.n}-nt random "
-                               f"ACGU RNA per GPU (seed {a.seed}+rank), rna_{a.params}, dangles 2; replicas",
-                   "n": a.n, "seed": a.seed, "params": a.params, "cells_per_fold": cells,
-                   "parallelism": f"replicas{world}"},
-        "sec_per_sequence": elapsed / a.steps, "nt_per_s": a.n * world * a.steps / elapsed,
-        "fill_ms": fill_ms / a.steps, "create_ms": create_ms, "energy": e,
+    out.update({
         "kernel_ms_instrumented_fold": kms,
         "roofline": roof(dom),
         "roofline_by_kernel": {k: roof(k) for k in kms},
-    }
+    })
     if world == 1 and not a.no_cpu_baseline:
         cb = pf_cpu_baseline(a.pf_cpu_sample_n, cores=a.cpu_cores)
         if cb:
@@ -326,7 +375,16 @@ def parse_args(argv=None):
     ap.add_argument("--pf-cpu-sample-n", type=int, default=80)
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the rank launch, barrier and max-over-ranks accounting only (tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0: energy, "
+                         "structure, W, the 2-D matrices) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes work of its own: the instrumented fold (per-kernel-family times and "
+                         "rooflines), the CPU baseline and the comparisons with the reference")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def find_traffic(n, seed, params, pf=False):
@@ -475,13 +533,18 @@ def main(argv=None):
     reset_s, level_ms, fill_ms = acc["reset_s"], acc["level_ms"], acc["fill_ms"]
     structure, energy = acc["last"].structure, acc["last"].energy
     wf = ctxs[0]
-    # after the timed region: one fold with marker events around every launch (per-kernel-family
-    # times for the interior loops (k_iloop) / k_diag2d; the
-    # markers slow that fold down, so it is not part of `value`)
-    wf.set_timing(2)
-    wf.ccj()
-    tmi = wf.timing()
-    il_ms, diag_ms, pp_ms = tmi["iloop_ms"], tmi["diag2d_ms"], tmi["ppush_ms"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mfe_outputs(acc["last"]))
+    tmi = None
+    il_ms = diag_ms = pp_ms = 0.0
+    if a.full:
+        # after the timed region: one fold with marker events around every launch (per-kernel-family
+        # times for the interior loops (k_iloop) / k_diag2d; the
+        # markers slow that fold down, so it is not part of `value`)
+        wf.set_timing(2)
+        wf.ccj()
+        tmi = wf.timing()
+        il_ms, diag_ms, pp_ms = tmi["iloop_ms"], tmi["diag2d_ms"], tmi["ppush_ms"]
     elapsed = max_over_ranks(elapsed, dist)
 
     wm = (ctypes.c_double * 4)()
@@ -565,10 +628,7 @@ def main(argv=None):
         "structure": structure,
         "rank0_last_seq_seed": a.seed if shard else rank_seed(a.seed, 0, world, a.steps - 1, a.distinct),
         "breakdown_ms": {"setup_reset": reset_s / a.steps * 1e3, "fill_device": fill_ms / a.steps,
-                         "level4d_levels": level_ms / a.steps,
-                         "iloop_kernels_instrumented_fold": il_ms, "diag2d_kernels_instrumented_fold": diag_ms,
-                         "ppush_kernels_instrumented_fold": pp_ms,
-                         "fill_instrumented_fold": tmi["fill_ms"]},
+                         "level4d_levels": level_ms / a.steps},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes/launch",
                      "traffic_source": traffic_src,
@@ -582,13 +642,28 @@ def main(argv=None):
                      # duration: the counter-based bandwidth fraction beside the algorithmic one
                      "frac_counter": (traffic / avg_launch_s / 1e9 / HBM_PEAK_GBS) if traffic and avg_launch_s > 0 else None,
                      "achieved_counter_gbs": (traffic / avg_launch_s / 1e9) if traffic and avg_launch_s > 0 else None},
-        "roofline_iloop": {"bound": "hbm", "achieved": il_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                           "frac": il_achieved / HBM_PEAK_GBS,
-                           "kernel": il_kernel + " (one instrumented fold after the timed region)",
-                           "launches_per_fold": max(a.n - 6, 1), "avg_launch_us": il_launch_s * 1e6,
-                           "algorithmic_bytes_per_fold": bytes_il, "traffic": il_traffic, "traffic_unit": "bytes/launch",
-                           "frac_counter": (il_traffic / il_launch_s / 1e9 / HBM_PEAK_GBS) if il_traffic and il_launch_s > 0 else None},
     }
+    # the algorithmic model charges every operand read (split-sharing and the caches serve many of
+    # them); when its bytes per fold exceed what HBM could move in the fold's time it is an
+    # effective-bandwidth figure, not an HBM fraction: say so on the line
+    alg_step_gbs = (bytes_lv + bytes_il) / sec_per_step / 1e9
+    out["algorithmic_gbs_per_step"] = alg_step_gbs
+    if alg_step_gbs > HBM_PEAK_GBS or out["roofline"]["frac"] > 1.0:
+        out["roofline"]["note"] = ("algorithmic bytes exceed the HBM peak: frac is an effective (cache-served) "
+                                   "bandwidth, not an HBM fraction; see frac_counter")
+    if not a.full:  # the plain run ends here: everything below takes the instrumented fold or runs of its own
+        print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    out["breakdown_ms"].update({"iloop_kernels_instrumented_fold": il_ms, "diag2d_kernels_instrumented_fold": diag_ms,
+                                "ppush_kernels_instrumented_fold": pp_ms, "fill_instrumented_fold": tmi["fill_ms"]})
+    out["roofline_iloop"] = {"bound": "hbm", "achieved": il_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": il_achieved / HBM_PEAK_GBS,
+                             "kernel": il_kernel + " (one instrumented fold after the timed region)",
+                             "launches_per_fold": max(a.n - 6, 1), "avg_launch_us": il_launch_s * 1e6,
+                             "algorithmic_bytes_per_fold": bytes_il, "traffic": il_traffic, "traffic_unit": "bytes/launch",
+                             "frac_counter": (il_traffic / il_launch_s / 1e9 / HBM_PEAK_GBS) if il_traffic and il_launch_s > 0 else None}
     # the side kernels in the fill (instrumented fold: marker events around every launch, so these
     # are in-fill durations with the level chain beside them, not standalone figures)
     pp_n = side_traffic.get("k_ppush", (None, max(a.n - 3, 1)))[1]
@@ -614,14 +689,6 @@ def main(argv=None):
                                "gbs": fb / (fill_ms / a.steps / 1e3) / 1e9,
                                "frac": fb / (fill_ms / a.steps / 1e3) / 1e9 / HBM_PEAK_GBS,
                                "source": traffic_src}
-    # the algorithmic model charges every operand read (split-sharing and the caches serve many of
-    # them); when its bytes per fold exceed what HBM could move in the fold's time it is an
-    # effective-bandwidth figure, not an HBM fraction: say so on the line
-    alg_step_gbs = (bytes_lv + bytes_il) / sec_per_step / 1e9
-    out["algorithmic_gbs_per_step"] = alg_step_gbs
-    if alg_step_gbs > HBM_PEAK_GBS or out["roofline"]["frac"] > 1.0:
-        out["roofline"]["note"] = ("algorithmic bytes exceed the HBM peak: frac is an effective (cache-served) "
-                                   "bandwidth, not an HBM fraction; see frac_counter")
     if world == 1 and not a.no_cpu_baseline:
         cb = cpu_baseline(a.cpu_sample_n, cores=a.cpu_cores)
         out["cpu_baseline"] = cb

@@ -64,6 +64,34 @@ def test_rank_seeds():
     assert [bench.rank_seed(5, 1, 2, k, True) for k in range(3)] == [6, 8, 10]
 
 
+def test_dump_outputs_files_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per array; past the byte cap an oversized array is cut to the
+    same sorted sample on every call, and the files together stay within the cap."""
+    np = pytest.importorskip("numpy")
+    big = [float(3 * x) for x in range(1000)]
+    bench.dump_outputs(str(tmp_path / "a"), {"energy": [-90.65], "big": big})
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "energy.npy"]
+    got = np.load(tmp_path / "a" / "big.npy")
+    assert got.dtype == np.float64 and got.tolist() == big
+    assert np.load(tmp_path / "a" / "energy.npy").tolist() == [-90.65]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 1600)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"energy": [-90.65], "big": big})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.size == 100 and b.tolist() == c.tolist() == sorted(set(b.tolist())) and set(b.tolist()) <= set(big)
+    assert np.load(tmp_path / "b" / "energy.npy").tolist() == [-90.65]
+    assert b.nbytes + 8 <= 1600
+
+
+def test_plain_and_full_flags():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_gpus_flag_spawns_ranks():
     """`bench.py --gpus 2` with no WORLD_SIZE starts two rank processes itself (gloo, no GPU in
     --dry-run) and rank 0 reports n_gpus 2 with both ranks present."""

@@ -6,11 +6,12 @@ Pinned by
     'x', DEF/INF/NST, shifted slices, update_nst, special-hairpin quirks, symmetry warnings,
     unknown identifiers and every fatal error — expected tables, stderr and exit status;
   * the bundled blobs ccj_amd/params/*.ccjp (ref_driver dumps of the reference's own parameter
-    files): when /root/reference/params is present the files themselves are parsed and must give
-    the same bytes (skipped elsewhere; the reference never travels).
+    files): the files themselves (tests/golden/params/*.par.gz, byte-for-byte copies) are parsed and
+    must give the same bytes.
 """
 import base64
 import ctypes
+import gzip
 import hashlib
 import os
 import zlib
@@ -23,7 +24,7 @@ import ccj_amd
 from ccj_amd import ParFileError, load_par
 
 PARAMS = os.path.join(ROOT, "ccj_amd", "params")
-REF_PARAMS = "/root/reference/params"
+REF_PARAMS = os.path.join(ROOT, "tests", "golden", "params")
 SETS = {"rna_Turner04": "Turner04", "rna_DirksPierce09": "DirksPierce09", "rna_DirksPierce03": "DirksPierce03",
         "rna_CaoChen06": "CaoChen06", "rna_CaoChen09": "CaoChen09", "dna_Matthews04": "Matthews04"}
 
@@ -130,17 +131,23 @@ def test_bad_base_rejected():
         load_par("## RNAfold parameter file v2.0\n", b"\0" * len(_base()), text=True)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference parameter files not present")
+def _ref_par(stem, tmp_path):
+    """The reference's own parameter file, unpacked from tests/golden/params/<stem>.par.gz."""
+    par = tmp_path / (stem + ".par")
+    with gzip.open(os.path.join(REF_PARAMS, stem + ".par.gz"), "rb") as f:
+        par.write_bytes(f.read())
+    return str(par)
+
+
 @pytest.mark.parametrize("stem", sorted(SETS))
-def test_reference_parameter_files_give_bundled_blobs(stem):
-    applied, blob, log = load_par(os.path.join(REF_PARAMS, stem + ".par"))
+def test_reference_parameter_files_give_bundled_blobs(stem, tmp_path):
+    applied, blob, log = load_par(_ref_par(stem, tmp_path))
     assert applied == 1
     assert blob == open(os.path.join(PARAMS, SETS[stem] + ".ccjp"), "rb").read()
     # dna_Matthews04.par has an asymmetric stack_enthalpies table: 4 warnings, like the reference
     assert log == ("WARNING: stacking enthalpies not symmetric\n" * 4 if stem == "dna_Matthews04" else "")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference parameter files not present")
-def test_load_params_reads_par_files_natively():
-    p = os.path.join(REF_PARAMS, "rna_Turner04.par")
+def test_load_params_reads_par_files_natively(tmp_path):
+    p = _ref_par("rna_Turner04", tmp_path)
     assert ccj_amd.load_params(p) == open(os.path.join(PARAMS, "Turner04.ccjp"), "rb").read()

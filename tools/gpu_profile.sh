@@ -1,7 +1,7 @@
 # Round profile artifacts (copied into profiles/ by tools/make_profiles.py):
 #   bash tools/gpu_profile.sh [mfe|n400|pf]
 #   mfe  (default): kt = --kernel-trace --stats of the bench command, FETCH_SIZE and WRITE_SIZE passes
-#                   (separate runs) of the fill kernels, then the default bench line (CPU baseline on)
+#                   (separate runs) of the fill kernels, then the bench line with --full (CPU baseline on)
 #   n400          : the two counter passes over bench.py --n 400 --seed 6 (config 5 per GPU)
 #   pf            : the counter passes and a kernel trace over bench.py --pf
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
@@ -19,7 +19,7 @@ fi
 timeout -k 10 -s KILL 600 rocprofv3 --kernel-trace --output-format csv --kernel-include-regex "$K" --pmc FETCH_SIZE -d $D/fetch -o f -- $B > $D/fetch.log 2>&1 && \
 timeout -k 10 -s KILL 600 rocprofv3 --kernel-trace --output-format csv --kernel-include-regex "$K" --pmc WRITE_SIZE -d $D/write -o w -- $B > $D/write.log 2>&1 || { echo "counter passes failed"; exit 1; }
 if [ "$what" = mfe ]; then
-  timeout -k 10 900 python3 bench.py > $D/bench_full.json 2> $D/bench_full.err || { echo "bench failed"; exit 1; }
+  timeout -k 10 900 python3 bench.py --full > $D/bench_full.json 2> $D/bench_full.err || { echo "bench failed"; exit 1; }
   cat $D/bench_full.json
 fi
 echo "profile $what ok"

@@ -12,7 +12,7 @@ def main(path):
     lev = [r for r in rows if name(r) == "k_pf_level"]
     diag = [r for r in rows if name(r) == "k_pf_diag"]
     il = [r for r in rows if name(r) == "k_pf_iloop"]
-    # the first fill of the trace (bench.py --pf --steps 1 --warmup 0: the timed fill, then one
+    # the first fill of the trace (bench.py --pf --full --steps 1 --warmup 0: the timed fill, then one
     # instrumented fill): its levels are the first n-2 k_pf_level launches, n-2 = launches / fills
     nlev = len(lev) // 2 if len(lev) % 2 == 0 else len(lev)
     lev = lev[:nlev]
