@@ -79,6 +79,15 @@ class _Problem(ctypes.Structure):
                 ("params", ctypes.c_void_p), ("pen", ctypes.c_void_p)]
 
 
+class _Penalties(ctypes.Structure):
+    """include/ccj_params.h ccj_pk_penalties"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("PS", "PSM", "PSP", "PB", "PUP", "PPS", "a", "b", "c", "ap", "bp", "cp")] + \
+               [("e_stP", ctypes.c_double), ("e_intP", ctypes.c_double)]
+
+
+PEN_DEFAULT = (-138, 1007, 1500, 246, 6, 96, 339, 3, 2, 341, 56, 12, 0.89, 0.74)  # CCJ_PK_PENALTIES_DEFAULT
+
+
 class _Options(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int), ("overlap_d2h", ctypes.c_int), ("shard_world", ctypes.c_int),
                 ("shard_rank", ctypes.c_int), ("shard_simulate", ctypes.c_int), ("host_traceback", ctypes.c_int),
@@ -286,7 +295,7 @@ class W_final:
                  noGU: bool = False, device: int = 0, overlap_d2h: bool = False, shard_world: int = 1,
                  shard_rank: int = 0, shard_simulate: bool = False, comm_id: Optional[bytes] = None,
                  host_traceback: bool = False, split_target: int = 0, share_splits: int = 0,
-                 local_group: Optional["LocalGroup"] = None):
+                 local_group: Optional["LocalGroup"] = None, pen=None):
         """shard_world > 1: band-shard this one sequence over shard_world processes (one per GPU),
         exchanging each level over RCCL; every rank passes the same comm_id (from comm_unique_id()
         on one rank), or the same local_group when the ranks are contexts of this process.
@@ -294,7 +303,10 @@ class W_final:
         host_traceback: run W and the traceback on the host over a mirror of every matrix (the
         reference restatement; overlap_d2h streams that mirror during the fill) instead of on the GPU.
         split_target / share_splits: level-kernel tuning (include/ccj.h ccj_options; 0 = default,
-        < 0 = never split a level / no split-point sharing)."""
+        < 0 = never split a level / no split-point sharing).
+        pen: the pseudoknot penalties (include/ccj_params.h ccj_pk_penalties), 14 values in the
+        struct's order: PS PSM PSP PB PUP PPS a b c ap bp cp (ints) e_stP e_intP (floats); None =
+        the reference's h_globals.hh defaults (PEN_DEFAULT)."""
         self.seq = seq
         self.n = len(seq)
         self.dangle = dangle
@@ -302,8 +314,14 @@ class W_final:
         self._blob_buf = ctypes.create_string_buffer(bytes(self._blob), len(self._blob))
         self._seq_buf = ctypes.create_string_buffer(seq.encode())
         L = lib()
+        self._pen = None
+        if pen is not None:
+            if len(pen) != 14:
+                raise CCJError(CCJ_E_ARG, "pen needs the 14 values of ccj_pk_penalties")
+            self._pen = _Penalties(*[int(v) for v in pen[:12]], float(pen[12]), float(pen[13]))
         prob = _Problem(ctypes.cast(self._seq_buf, ctypes.c_char_p), dangle, 1 if noGU else 0,
-                        ctypes.cast(self._blob_buf, ctypes.c_void_p), None)
+                        ctypes.cast(self._blob_buf, ctypes.c_void_p),
+                        ctypes.cast(ctypes.pointer(self._pen), ctypes.c_void_p) if self._pen is not None else None)
         opts = _Options(device, 1 if overlap_d2h else 0, shard_world, shard_rank, 1 if shard_simulate else 0,
                         1 if host_traceback else 0, split_target, share_splits)
         h = ctypes.c_void_p()

@@ -253,9 +253,11 @@ def _main(a, stdin):
     return code, out, err + ferr
 
 
-def fold_cli(seq: str, params, dangles: int, noGU: bool, device: int = 0):
-    """One CCJ invocation -> (exit code, stdout text, stderr text), as the reference prints them."""
-    wf = W_final(seq, dangles, params=params, noGU=noGU, device=device)
+def fold_cli(seq: str, params, dangles: int, noGU: bool, device: int = 0, pen=None, **engine):
+    """One CCJ invocation -> (exit code, stdout text, stderr text), as the reference prints them.
+    pen: the 14 pseudoknot penalties (W_final's keyword; None = the reference's defaults); further
+    keywords (host_traceback=...) go to W_final unchanged."""
+    wf = W_final(seq, dangles, params=params, noGU=noGU, device=device, pen=pen, **engine)
     try:
         energy = wf.ccj()
     except BacktrackExit as e:

@@ -33,7 +33,12 @@ enum BtStatus : int {
     BT_INTER = 2,      // "NOT GOOD RESTR INTER, ..." then exit(0) (W_final.cc:224-225)
     BT_ASSERT = 3,     // Matrix4D::get_uc assert (matrices.hh:167), exit 134
     BT_OVERFLOW = 4,   // device stack capacity exceeded (engine limit, not a reference exit)
+    BT_STEPS = 5,      // BT_MAX_STEPS nodes processed without emptying the stack (engine limit)
 };
+// Step limit of the device traceback.  A traceback of the reference pops O(n) nodes per pair it
+// sets (a cell changes type a few times before it shrinks), so even n = 1000 stays far below it;
+// it only ends a walk that would otherwise never terminate.
+constexpr int BT_MAX_STEPS = 1 << 22;
 // message prefixes of the reference's "This should not have happened!" exits
 constexpr int BT_NPREFIX = 7;
 inline const char *bt_prefix(int p) {

@@ -1228,6 +1228,10 @@ __global__ __launch_bounds__(64 * BT_MAXW) void k_backtrack(DevTables T, const i
     B.push2(1, n, FREE);  // W_final.cc:84-99
     __syncthreads();
     while (B.sp > 0 && B.st.status == BT_OK) {
+        if (B.st.steps >= BT_MAX_STEPS) {  // uniform: every lane counts the same steps
+            B.st.status = BT_STEPS;
+            break;
+        }
         const Interval cur = stk[B.sp - 1];
         __syncthreads();  // every lane has read the top before lane 0 overwrites it
         --B.sp;

@@ -2591,6 +2591,8 @@ int result_finish(ccj_ctx *c, std::string &structure, std::string &out, std::chr
         case BT_ASSERT:
             c->err = "CCJ: matrices.hh:167: Assertion `!(i<=0 || l> n_)' failed.\n";
             return CCJ_E_BACKTRACK;
+        case BT_STEPS:
+            return set_err(c, CCJ_E_HIP, "device traceback did not end within %d steps", BT_MAX_STEPS);
         default:
             return set_err(c, CCJ_E_HIP, "device traceback stack overflow (capacity %d)", cap);
     }

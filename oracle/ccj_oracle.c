@@ -685,14 +685,16 @@ static int E_ext_Stem(const oracle *o, int vij, int vi1j, int vij1, int vi1j1, i
 /* ------------------------------------------------------------------------------------------ */
 void ccj_oracle_free(oracle *o);
 
-static oracle *oracle_alloc(const char *seq, const ccj_energy_params *P, int dangles, int noGU) {
+/* pen == NULL: the reference's h_globals.hh defaults */
+static oracle *oracle_alloc(const char *seq, const ccj_energy_params *P, int dangles, int noGU,
+                            const ccj_pk_penalties *penp) {
     oracle *o = (oracle *)calloc(1, sizeof(oracle));
     int n = (int)strlen(seq);
     o->n = n;
     o->dangles = dangles;
     o->P = P;
     ccj_pk_penalties pen = CCJ_PK_PENALTIES_DEFAULT;
-    o->pen = pen;
+    o->pen = penp ? *penp : pen;
     o->seq = strdup(seq);
     /* make_pair_matrix, pair_mat.h:81-155 */
     int base_rtype[8] = {0, 2, 1, 4, 3, 6, 5, 7};
@@ -776,8 +778,9 @@ static void oracle_exterior(oracle *o) {
 }
 
 
-oracle *ccj_oracle_fold(const char *seq, const ccj_energy_params *P, int dangles, int noGU) {
-    oracle *o = oracle_alloc(seq, P, dangles, noGU);
+oracle *ccj_oracle_fold_pen(const char *seq, const ccj_energy_params *P, int dangles, int noGU,
+                            const ccj_pk_penalties *pen) {
+    oracle *o = oracle_alloc(seq, P, dangles, noGU, pen);
     if (!o) return NULL;
     int n = o->n;
     /* fill, W_final.cc:60-67 and pseudo_loop.cc:69-132 */
@@ -794,6 +797,10 @@ oracle *ccj_oracle_fold(const char *seq, const ccj_energy_params *P, int dangles
         }
     oracle_exterior(o);
     return o;
+}
+
+oracle *ccj_oracle_fold(const char *seq, const ccj_energy_params *P, int dangles, int noGU) {
+    return ccj_oracle_fold_pen(seq, P, dangles, noGU, NULL);
 }
 
 /*
@@ -835,13 +842,14 @@ static void fill_level(oracle *o, int t) {
     }
 }
 
-oracle *ccj_oracle_fold_par(const char *seq, const ccj_energy_params *P, int dangles, int noGU, int nthreads) {
+oracle *ccj_oracle_fold_par_pen(const char *seq, const ccj_energy_params *P, int dangles, int noGU, int nthreads,
+                                const ccj_pk_penalties *pen) {
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #else
     (void)nthreads;
 #endif
-    oracle *o = oracle_alloc(seq, P, dangles, noGU);
+    oracle *o = oracle_alloc(seq, P, dangles, noGU, pen);
     if (!o) return NULL;
     int n = o->n;
     int progress = getenv("CCJ_ORACLE_PROGRESS") != NULL;
@@ -852,6 +860,10 @@ oracle *ccj_oracle_fold_par(const char *seq, const ccj_energy_params *P, int dan
     }
     oracle_exterior(o);
     return o;
+}
+
+oracle *ccj_oracle_fold_par(const char *seq, const ccj_energy_params *P, int dangles, int noGU, int nthreads) {
+    return ccj_oracle_fold_par_pen(seq, P, dangles, noGU, nthreads, NULL);
 }
 
 void ccj_oracle_free(oracle *o) {

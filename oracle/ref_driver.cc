@@ -6,6 +6,8 @@
 //   fold         run W_final(seq,dangle).ccj() exactly as src/CCJ.cc:44-49,104-108 does and print
 //                the same two stdout lines; optionally print FNV-1a hashes of every DP matrix in
 //                the canonical (i,j,k,l) order and dump them for byte-level diffs.
+//                --pen V1,...,V14 assigns the reference's penalty globals (h_globals.hh) first,
+//                in the order of ccj_pk_penalties (include/ccj_params.h); also for hash.
 //   dump-params  write the scaled vrna_param_t fields the CCJ path reads into our blob format
 //                (include/ccj_params.h) — this is how tests/golden/params/*.ccjp are produced.
 // Parameters can come from a .par file (-P, as the reference CLI), the DNA Mathews 2004 set
@@ -163,7 +165,43 @@ struct Opts {
     std::string parfile, blob, dump, out;
     bool dna = false, timing = false, hash = false;
     std::string seq;
+    bool has_pen = false;  // --pen: the 14 values of ccj_pk_penalties, in the struct's order
+    ccj_pk_penalties pen;
 };
+
+// --pen: assign the reference's mutable penalty globals (h_globals.hh:7-25) before the fold.
+static void apply_pen(const Opts &o) {
+    if (!o.has_pen) return;
+    const ccj_pk_penalties &p = o.pen;
+    PS_penalty = p.PS; PSM_penalty = p.PSM; PSP_penalty = p.PSP;
+    PB_penalty = p.PB; PUP_penalty = p.PUP; PPS_penalty = p.PPS;
+    a_penalty = p.a; b_penalty = p.b; c_penalty = p.c;
+    ap_penalty = p.ap; bp_penalty = p.bp; cp_penalty = p.cp;
+    e_stP_penalty = p.e_stP; e_intP_penalty = p.e_intP;
+}
+
+// "PS,PSM,PSP,PB,PUP,PPS,a,b,c,ap,bp,cp,e_stP,e_intP" (commas or spaces inside one argument)
+static bool parse_pen(const char *s, ccj_pk_penalties &p) {
+    double v[14];
+    int k = 0;
+    char *end;
+    while (k < 14) {
+        while (*s == ',' || *s == ' ') ++s;
+        if (!*s) break;
+        v[k++] = strtod(s, &end);
+        if (end == s) return false;
+        s = end;
+    }
+    while (*s == ',' || *s == ' ') ++s;
+    if (k != 14 || *s) return false;
+    int32_t *ip = &p.PS;
+    for (int x = 0; x < 6; ++x) ip[x] = (int32_t)v[x];
+    ip = &p.a;
+    for (int x = 0; x < 6; ++x) ip[x] = (int32_t)v[6 + x];
+    p.e_stP = v[12];
+    p.e_intP = v[13];
+    return true;
+}
 
 static int load_params(const Opts &o) {
     if (!o.blob.empty()) {
@@ -266,6 +304,7 @@ static void hash_all(const Opts &o, W_final &wf, int n) {
 static int cmd_fold(const Opts &o) {
     noGU = o.noGU ? 1 : 0;
     if (load_params(o)) return 1;
+    apply_pen(o);
     std::string seq = o.seq;
     auto t0 = std::chrono::steady_clock::now();
     W_final wf(seq, o.dangles);
@@ -289,6 +328,7 @@ static int cmd_fold(const Opts &o) {
 static int cmd_hash(const Opts &o) {
     noGU = o.noGU ? 1 : 0;
     if (load_params(o)) return 1;
+    apply_pen(o);
     std::string seq = o.seq;
     W_final wf(seq, o.dangles);
     int n = (int)seq.size();
@@ -348,6 +388,13 @@ int main(int argc, char **argv) {
         else if (s == "--hash") o.hash = true;
         else if (s == "--dump" && a + 1 < argc) o.dump = argv[++a];
         else if (s == "-o" && a + 1 < argc) o.out = argv[++a];
+        else if (s == "--pen" && a + 1 < argc) {
+            if (!parse_pen(argv[++a], o.pen)) {
+                fprintf(stderr, "ref_driver: --pen needs 14 comma-separated values\n");
+                return 2;
+            }
+            o.has_pen = true;
+        }
         else o.seq = s;
     }
     if (cmd == "fold") {

@@ -6,7 +6,9 @@ engine never does.  If oracle/_ref/libccj_oracle.so is absent it is compiled wit
 import ctypes
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "_ref", "libccj_oracle.so")
@@ -20,17 +22,40 @@ HASH_NAMES = ["PK", "PL", "PR", "PM", "PO", "PfromL", "PfromR", "PfromM", "Pfrom
 _lib = None
 
 
+class PkPenalties(ctypes.Structure):
+    """include/ccj_params.h ccj_pk_penalties"""
+    _fields_ = [(k, ctypes.c_int32) for k in ("PS", "PSM", "PSP", "PB", "PUP", "PPS", "a", "b", "c", "ap", "bp", "cp")] + \
+               [("e_stP", ctypes.c_double), ("e_intP", ctypes.c_double)]
+
+
 def oracle_lib():
     global _lib
     if _lib is None:
+        make = ["make", "-C", os.path.join(ROOT, "oracle"), "oracle"]
         if not os.path.exists(ORACLE_SO):
-            subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "oracle"], check=True,
-                           capture_output=True)
-        L = ctypes.CDLL(ORACLE_SO)
+            subprocess.run(make, capture_output=True)
+        L = ctypes.CDLL(ORACLE_SO) if os.path.exists(ORACLE_SO) else None
+        if L is None or not hasattr(L, "ccj_oracle_fold_par_pen"):
+            # oracle/_ref cannot be written, or holds a library left over from an older
+            # ccj_oracle.c (whatever its timestamp says, whoever owns it): build the current source
+            # into a directory of our own and load that file; dlopen() would hand back the image it
+            # already holds for ORACLE_SO
+            tmp = tempfile.mkdtemp(prefix="ccj_oracle_")
+            try:
+                subprocess.run(make + ["OUT=" + tmp], check=True, capture_output=True)
+                L = ctypes.CDLL(os.path.join(tmp, "libccj_oracle.so"))
+            finally:
+                shutil.rmtree(tmp, ignore_errors=True)
         L.ccj_oracle_fold.restype = ctypes.c_void_p
         L.ccj_oracle_fold.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int]
         L.ccj_oracle_fold_par.restype = ctypes.c_void_p
         L.ccj_oracle_fold_par.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.ccj_oracle_fold_pen.restype = ctypes.c_void_p
+        L.ccj_oracle_fold_pen.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(PkPenalties)]
+        L.ccj_oracle_fold_par_pen.restype = ctypes.c_void_p
+        L.ccj_oracle_fold_par_pen.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.POINTER(PkPenalties)]
         L.ccj_oracle_hashes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.ccj_oracle_free.argtypes = [ctypes.c_void_p]
         L.ccj_oracle_W.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -47,16 +72,22 @@ def oracle_lib():
 class OracleFold:
     """CPU restatement of the fill for one sequence (reference loop order)."""
 
-    def __init__(self, seq, blob: bytes, dangles=2, noGU=0, threads=None):
+    def __init__(self, seq, blob: bytes, dangles=2, noGU=0, threads=None, pen=None):
         """threads=None: the sequential fill in the reference's own loop order; threads=k (0: all
-        cores): the level-parallel restatement (ccj_oracle_fold_par, OpenMP)."""
+        cores): the level-parallel restatement (ccj_oracle_fold_par, OpenMP).  pen: None (the
+        reference's h_globals.hh defaults) or the 14 values of ccj_pk_penalties in struct order."""
         L = oracle_lib()
         self._blob = ctypes.create_string_buffer(blob, len(blob))
         self.n = len(seq)
+        penp = None
+        if pen is not None:
+            if len(pen) != 14:
+                raise ValueError("pen needs the 14 values of ccj_pk_penalties")
+            penp = ctypes.byref(PkPenalties(*[int(v) for v in pen[:12]], float(pen[12]), float(pen[13])))
         if threads is None:
-            self.h = L.ccj_oracle_fold(seq.encode(), self._blob, dangles, noGU)
+            self.h = L.ccj_oracle_fold_pen(seq.encode(), self._blob, dangles, noGU, penp)
         else:
-            self.h = L.ccj_oracle_fold_par(seq.encode(), self._blob, dangles, noGU, threads)
+            self.h = L.ccj_oracle_fold_par_pen(seq.encode(), self._blob, dangles, noGU, threads, penp)
         if not self.h:
             raise MemoryError("oracle allocation failed")
 
