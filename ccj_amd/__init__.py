@@ -301,7 +301,7 @@ class W_final:
         on one rank), or the same local_group when the ranks are contexts of this process.
         shard_simulate runs all shards in this one context without an exchange.
         host_traceback: run W and the traceback on the host over a mirror of every matrix (the
-        reference restatement; overlap_d2h streams that mirror during the fill) instead of on the GPU.
+        same node logic, host executor; overlap_d2h streams that mirror during the fill) instead of on the GPU.
         split_target / share_splits: level-kernel tuning (include/ccj.h ccj_options; 0 = default,
         < 0 = never split a level / no split-point sharing).
         pen: the pseudoknot penalties (include/ccj_params.h ccj_pk_penalties), 14 values in the

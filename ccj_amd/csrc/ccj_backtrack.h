@@ -1,5 +1,5 @@
-// ccj_backtrack.h — backtrack node types and the exit records shared by the host traceback
-// (ccj_host.cc, over the host mirror) and the device traceback (ccj_backtrack.hip).
+// ccj_backtrack.h — backtrack node types and the exit record of the traceback: what the node logic
+// (ccj_traceback.h) and its two executors, device (ccj_backtrack.hip) and host (ccj_host.cc), share.
 #pragma once
 #include <stdint.h>
 
@@ -26,7 +26,8 @@ struct Interval {  // reference h_struct.hh:65-92 (seq_interval)
     int type;  // one of the chars above
 };
 
-// How a traceback ended (device record; the host turns it into the reference's exit).
+// How a traceback ended (either executor fills it; bt_exit in ccj_host.cc turns it into the
+// reference's messages and return code).
 enum BtStatus : int {
     BT_OK = 0,
     BT_DIE = 1,        // exit(EXIT_FAILURE) after "<prefix>This should not have happened!, <case>"
@@ -35,7 +36,7 @@ enum BtStatus : int {
     BT_OVERFLOW = 4,   // device stack capacity exceeded (engine limit, not a reference exit)
     BT_STEPS = 5,      // BT_MAX_STEPS nodes processed without emptying the stack (engine limit)
 };
-// Step limit of the device traceback.  A traceback of the reference pops O(n) nodes per pair it
+// Step limit of the traceback, on both executors.  A traceback of the reference pops O(n) nodes per pair it
 // sets (a cell changes type a few times before it shrinks), so even n = 1000 stays far below it;
 // it only ends a walk that would otherwise never terminate.
 constexpr int BT_MAX_STEPS = 1 << 22;

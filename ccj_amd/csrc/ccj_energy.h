@@ -25,6 +25,19 @@ constexpr int TURN = CCJ_TURN;
 constexpr int MAXLOOP = CCJ_MAXLOOP;
 constexpr int INTERN_INF = 32767;
 
+// Names the plain C++ traceback (ccj_traceback.h) shares with the engine (ccj_engine.h): the 22
+// 4-D gap matrices and the pseudoknot penalties.
+constexpr int NMAT4 = 22;
+enum Mat4 {
+    PK = 0, PL, PR, PM, PO, PfromL, PfromR, PfromM, PfromMprime, PfromO,
+    PLmloop00, PLmloop01, PLmloop10, PRmloop00, PRmloop01, PRmloop10,
+    PMmloop00, PMmloop01, PMmloop10, POmloop00, POmloop01, POmloop10
+};
+
+struct Penalties {  // integer PK penalties, h_globals.hh:7-25
+    int PS, PSM, PSP, PB, PUP, PPS, a, b, c, ap, bp, cp;
+};
+
 CCJ_HD int imin(int a, int b) { return a < b ? a : b; }
 CCJ_HD int imax(int a, int b) { return a > b ? a : b; }
 

@@ -15,16 +15,10 @@
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "ccj_energy.h"  // Mat4, Penalties
 #include "ccj_params.h"
 
 namespace ccj {
-
-constexpr int NMAT4 = 22;
-enum Mat4 {
-    PK = 0, PL, PR, PM, PO, PfromL, PfromR, PfromM, PfromMprime, PfromO,
-    PLmloop00, PLmloop01, PLmloop10, PRmloop00, PRmloop01, PRmloop10,
-    PMmloop00, PMmloop01, PMmloop10, POmloop00, POmloop01, POmloop10
-};
 
 // The matrices the loop records carry (below), which d4 does not store unless DevTables::mat5: the 5
 // no fill kernel reads back as matrices and 6 more the level kernel's stack terms read from the
@@ -193,10 +187,6 @@ __host__ __device__ __forceinline__ int xch_nmax(int t, int G, int part) {
 struct LvlX {        // per-level bases of the interior-loop copies
     long long lbx;  // element offset of level t in d4x: PLx (C_t elements) then PRx (C_t)
     long long pmb;  // element offset of level t in pmx: m_t * n * (t+1) elements
-};
-
-struct Penalties {  // integer PK penalties, h_globals.hh:7-25
-    int PS, PSM, PSP, PB, PUP, PPS, a, b, c, ap, bp, cp;
 };
 
 struct DevTables {

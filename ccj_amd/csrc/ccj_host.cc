@@ -1,13 +1,13 @@
 // ccj_host.cc — host side of libccj_hip.so: context + HBM allocation, sequence tables,
 // level-by-level kernel schedule on a HIP stream, overlapped D2H of finished levels into a
-// pinned host mirror, the exterior W array, and the host backtrack / bracket emission.
+// pinned host mirror, the way out of a traceback (exit record to the reference's messages and
+// return code) and the bracket emission.
 //
-// The backtrack and emission are restated from the reference so the output is bit-identical,
-// including its quirks:
+// The traceback's node logic is ccj_traceback.h, restated from the reference so the output is
+// bit-identical, including its quirks.  It runs on the GPU
+// (ccj_backtrack.hip); with ccj_options::host_traceback the same logic runs here through a small
+// host executor over the mirror (HostStore, HostExec).  This file restates:
 //   W_final::ccj (exterior W + driver)   reference src/W_final.cc:58-105
-//   W_final::E_ext_Stem                   reference src/W_final.cc:118-173
-//   W_final::backtrack                    reference src/W_final.cc:175-719
-//   pseudo_loop::backtrack                reference src/pseudo_loop.cc:861-2820
 //   W_final::fill_structure               reference src/W_final.cc:764-819
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -33,6 +33,7 @@
 #include "ccj_energy.h"
 #include "ccj_engine.h"
 #include "ccj_backtrack.h"
+#include "ccj_traceback.h"
 #include "ccj_items.h"
 
 using namespace ccj;
@@ -42,11 +43,6 @@ namespace {
 const int BP_PAIR[8][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 5, 0, 0, 5}, {0, 0, 0, 1, 0, 0, 0, 0},
                            {0, 0, 2, 0, 3, 0, 0, 0}, {0, 6, 0, 4, 0, 0, 0, 6}, {0, 0, 0, 0, 0, 0, 2, 0},
                            {0, 0, 0, 0, 0, 1, 0, 0}, {0, 6, 0, 0, 5, 0, 0, 0}};
-
-struct BacktrackExit {  // reference exit(...) inside the backtrack
-    int code;
-    std::string stderr_msg;
-};
 
 template <class T>
 struct DevBuf {
@@ -234,7 +230,6 @@ int set_err(ccj_ctx *c, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return set_err((ctx), CCJ_E_HIP, "%s: %s", #x, hipGetErrorString(e_));     \
     } while (0)
 
-enum { A2_V = 0, A2_WM, A2_WMV, A2_WMP, A2_P, A2_WBP, A2_WPP, A2_WB, A2_WP, A2_N };
 
 // --------------------------------------------------------------------------------------------
 // host energy helpers
@@ -267,1150 +262,196 @@ int E_Hairpin_host(const ccj_energy_params *P, const int *lx, int size, int type
 }
 
 // --------------------------------------------------------------------------------------------
-// The host-side view used by W + backtrack: reference getters over the mirror.
+// Host executor of the traceback (ccj_traceback.h): the host mirror as its Store, scans as
+// sequential loops.  A test-only option (ccj_options::host_traceback); the device executor is
+// ccj_backtrack.hip.
 // --------------------------------------------------------------------------------------------
-struct HostView {
-    ccj_ctx *c;
+struct HostStore {
+    const ccj_ctx *c;
     int n;
     const short *S, *S1;
-    const ccj_energy_params *P;
-    const int *lx;
+    const int *W;
 
-    explicit HostView(ccj_ctx *cc) : c(cc), n(cc->n), S(cc->S.data()), S1(cc->S1.data()), P(&cc->prm), lx(cc->lx.data()) {}
-
+    explicit HostStore(const ccj_ctx *cc) : c(cc), n(cc->n), S(cc->S.data()), S1(cc->S1.data()), W(cc->W.data()) {}
     int pr(int i, int j) const { return c->pair[S[i]][S[j]]; }
-    // s_energy_matrix.hh:37-43
-    int V(int i, int j) const { return i >= j ? INF : c->raw2(A2_V, i, j); }
-    char Vtype(int i, int j) const { return (char)c->hvt[c->a2(i, j)]; }
-    int WM(int i, int j) const { return i >= j ? INF : c->raw2(A2_WM, i, j); }
-    int WMv(int i, int j) const { return i >= j ? INF : c->raw2(A2_WMV, i, j); }
-    int WMp(int i, int j) const { return i >= j ? INF : c->raw2(A2_WMP, i, j); }
-    // TriangleMatrix::get (matrices.hh:38-41)
-    int Pg(int i, int j) const { return i > j ? INF : c->raw2(A2_P, i, j); }
-    int WBPg(int i, int j) const { return i > j ? INF : c->raw2(A2_WBP, i, j); }
-    int WPPg(int i, int j) const { return i > j ? INF : c->raw2(A2_WPP, i, j); }
-    // pseudo_loop.cc:647-661
-    int WB(int i, int j) const {
-        if (i <= 0 || j <= 0 || i > n || j > n) return INF;
-        if (i > j) return 0;
-        return std::min(c->pen.cp * (j - i + 1), WBPg(i, j));
-    }
-    int WP(int i, int j) const {
-        if (i <= 0 || j <= 0 || i > n || j > n) return INF;
-        if (i > j) return 0;
-        return std::min(c->pen.PUP * (j - i + 1), WPPg(i, j));
-    }
-    // Matrix4D::get (matrices.hh:177-182); get_uc's assert (matrices.hh:167) is live in the
-    // reference build, so an in-order but out-of-range cell aborts there.
-    int g4(int x, int i, int j, int k, int l) const {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (i <= 0 || l > n) throw BacktrackExit{134, "CCJ: matrices.hh:167: Assertion `!(i<=0 || l> n_)' failed.\n"};
+    int rt(int type) const { return c->rtype[type]; }
+    const ccj_energy_params *prm() const { return &c->prm; }
+    const int *lx() const { return c->lx.data(); }
+    const Penalties &pen() const { return c->pen; }
+    int dangles() const { return c->dangles; }
+    double est() const { return c->e_stP; }
+    double eint() const { return c->e_intP; }
+    int raw2(int which, int i, int j) const { return c->raw2(which, i, j); }
+    int Vtype(int i, int j) const { return c->hvt[c->a2(i, j)]; }
+    int raw4(int x, int i, int j, int k, int l) const {
         const int t = (j - i) + (l - k);
-        const LevelDesc &L = c->lv_host[t];
-        const int64_t off = c->lv_offh[t] + cell_offset_host(L, x, j - i, k - j - 2, i);
-        return (int)c->h4[off];
+        return (int)c->h4[c->lv_offh[t] + cell_offset_host(c->lv_host[t], x, j - i, k - j - 2, i)];
     }
-    bool can_pair(int i, int j) const {  // pseudo_loop.hh:131-135 (assert(i<=j) live in reference)
-        if (j - i <= TURN) return false;
-        return pr(i, j) > 0;
-    }
-    // pseudo_loop.cc:822-840
-    int compute_int(int i, int j, int k, int l) const {
-        return E_IntLoop(P, lx, k - i - 1, j - l - 1, pr(i, j), c->rtype[pr(k, l)], S1[i + 1], S1[j - 1], S1[k - 1],
-                         S1[l + 1]);
-    }
-    int e_stP(int i, int j) const {
-        if (i + 1 == j - 1) return INF;
-        return (int)lrint(c->e_stP * compute_int(i, j, i + 1, j - 1));
-    }
-    int e_intP(int i, int ip, int jp, int j) const { return (int)lrint(c->e_intP * compute_int(i, j, ip, jp)); }
-    int PfromMdoubleprime(int i, int j, int k, int l) const {  // pseudo_loop.cc:663-679
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (i == j && k == l) return pr(i, l) == 0 ? INF : 0;
-        return std::min(g4(PL, i, j, k, l) + c->pen.PB, g4(PR, i, j, k, l) + c->pen.PB);
-    }
+    unsigned pk(int i, int l) const { return (unsigned)(c->h_pk[c->a2(i, l)] & 0xffffffffull); }
 };
+using MirrorView = View<HostStore>;
 
-// --------------------------------------------------------------------------------------------
-// W (W_final.cc:68-79) and E_ext_Stem (W_final.cc:118-173)
-// --------------------------------------------------------------------------------------------
-int E_ext_Stem(const HostView &H, int dangles, int vij, int vi1j, int vij1, int vi1j1, int i, int j) {
-    const short *S = H.S;
-    const int n = H.n;
-    int e = INF, en;
-    int tt = H.pr(i, j);
-    en = vij;
-    if (en != INF) {
-        if (dangles == 2) en += E_ExtLoop(H.P, tt, i > 1 ? S[i - 1] : -1, j < n ? S[j + 1] : -1);
-        else en += E_ExtLoop(H.P, tt, -1, -1);
-        e = std::min(e, en);
-    }
-    if (dangles == 1) {
-        tt = H.pr(i + 1, j);
-        en = (j - i - 1 > TURN) ? vi1j : INF;
-        if (en != INF) en += E_ExtLoop(H.P, tt, S[i], -1);
-        e = std::min(e, en);
-        tt = H.pr(i, j - 1);
-        en = (j - 1 - i > TURN) ? vij1 : INF;
-        if (en != INF) en += E_ExtLoop(H.P, tt, -1, S[j]);
-        e = std::min(e, en);
-        tt = H.pr(i + 1, j - 1);
-        en = (j - 1 - i - 1 > TURN) ? vi1j1 : INF;
-        if (en != INF) en += E_ExtLoop(H.P, tt, S[i], S[j]);
-        e = std::min(e, en);
-    }
-    return e;
-}
-
+// W (W_final.cc:68-79)
 void compute_W(ccj_ctx *c) {
-    HostView H(c);
     const int n = c->n;
     c->W.assign(n + 1, 0);
+    const MirrorView H{HostStore(c)};
     std::vector<int> &W = c->W;
     for (int j = TURN + 1; j <= n; j++) {
         int m1 = W[j - 1], m2 = INF, m3 = INF;
         for (int k = 1; k <= j - TURN - 1; ++k) {
             const int acc = (k > 1) ? W[k - 1] : 0;
-            m2 = std::min(m2, acc + E_ext_Stem(H, c->dangles, H.V(k, j), H.V(k + 1, j), H.V(k, j - 1), H.V(k + 1, j - 1), k, j));
+            m2 = std::min(m2, acc + E_ext_Stem(H, H.V(k, j), H.V(k + 1, j), H.V(k, j - 1), H.V(k + 1, j - 1), k, j));
             m3 = std::min(m3, acc + std::min({H.Pg(k, j), H.Pg(k + 1, j), H.Pg(k, j - 1), H.Pg(k + 1, j - 1)}) + c->pen.PS);
         }
         W[j] = std::min({m1, m2, m3});
     }
 }
 
-// --------------------------------------------------------------------------------------------
-// Backtrack
-// --------------------------------------------------------------------------------------------
-struct Minfold {  // h_struct.hh:9-19
-    int pair = -1;
-    char type = T_NONE;
-};
-
-struct Backtracker {
-    const HostView &H;
-    ccj_ctx *c;
-    int n;
+struct HostExec {
+    const MirrorView &H;
     std::vector<Interval> stk;  // LIFO; back() is the top (reference insert_node pushes on the head)
-    std::vector<Minfold> f;
-    std::string structure;
-    std::string out;  // reference stdout side channel
-    const Penalties &pe;
+    std::vector<int> f_pair;    // h_struct.hh:9-19
+    std::vector<int8_t> f_type;
+    BtOut st{};
 
-    Backtracker(const HostView &h, ccj_ctx *cc)
-        : H(h), c(cc), n(cc->n), f(cc->n + 1), structure(cc->n + 1, '.'), pe(cc->pen) {}
-
-    void push2(int i, int j, char type) { stk.push_back(Interval{i, j, 0, 0, type}); }
-    // pseudo_loop::insert_node(i, j, k, l, type): fields i, j(=l of the region), k(=j), l(=k)
-    void push4(int i, int j, int k, int l, char type) { stk.push_back(Interval{i, j, k, l, type}); }
-    [[noreturn]] void die(const char *msg) { throw BacktrackExit{1, std::string(msg) + "\n"}; }
-
-    void run() {
-        // W_final.cc:84-99
-        push2(1, n, FREE);
-        while (!stk.empty()) {
-            Interval cur = stk.back();
-            stk.pop_back();
-            wf_backtrack(cur);
-        }
-    }
-
-    // W_final::backtrack, W_final.cc:175-719
-    void wf_backtrack(const Interval &cur) {
-        switch (cur.type) {
-            case LOOP: bt_loop(cur); break;
-            case FREE: bt_free(cur); break;
-            case M_WM: bt_wm(cur); break;
-            case M_WMv: bt_wmv(cur); break;
-            case M_WMp: bt_wmp(cur); break;
-            case P_PK: case P_PL: case P_PR: case P_PM: case P_PO: case P_PfromL: case P_PfromR: case P_PfromM:
-            case P_PfromO: case P_PLiloop: case P_PLiloop5: case P_PLmloop: case P_PLmloop00: case P_PLmloop01:
-            case P_PLmloop10: case P_PRiloop: case P_PRiloop5: case P_PRmloop: case P_PRmloop00: case P_PRmloop01:
-            case P_PRmloop10: case P_PMiloop: case P_PMiloop5: case P_PMmloop: case P_PMmloop00: case P_PMmloop01:
-            case P_PMmloop10: case P_POiloop: case P_POiloop5: case P_POmloop: case P_POmloop00: case P_POmloop01:
-            case P_POmloop10: case P_WB: case P_WBP: case P_WP: case P_WPP: case P_P:
-                pl_backtrack(cur);
-                break;
-            default:
-                out += "Should not be here!\n";  // A-B1: P_PfromMprime / P_PfromMdoubleprime land here
-        }
-    }
-
-    void bt_loop(const Interval &cur) {
-        const int i = cur.i, j = cur.j;
-        if (i >= j) return;
-        f[i].pair = j;
-        f[j].pair = i;
-        structure[i] = '(';
-        structure[j] = ')';
-        const char type = H.Vtype(i, j);
-        switch (type) {
-            case T_HAIRP:
-                f[i].type = T_HAIRP;
-                f[j].type = T_HAIRP;
-                break;
-            case T_INTER: {
-                f[i].type = T_INTER;
-                f[j].type = T_INTER;
-                int best_ip = j, best_jp = i;
-                int mn = INF;
-                const int max_ip = std::min(j - TURN - 2, i + MAXLOOP + 1);
-                for (int k = i + 1; k <= max_ip; ++k) {
-                    const int min_l = std::max(k + TURN + 1 + MAXLOOP + 2, k + j - i) - MAXLOOP - 2;
-                    for (int l = j - 1; l >= min_l; --l) {
-                        // s_energy_matrix::compute_int (:309-313): E_IntLoop + V(k,l)
-                        const int tmp = E_IntLoop(H.P, H.lx, k - i - 1, j - l - 1, H.pr(i, j), c->rtype[H.pr(k, l)],
-                                                  H.S1[i + 1], H.S1[j - 1], H.S1[k - 1], H.S1[l + 1]) + H.V(k, l);
-                        if (tmp < mn) { mn = tmp; best_ip = k; best_jp = l; }
-                    }
-                }
-                if (best_ip < best_jp) push2(best_ip, best_jp, LOOP);
-                else {
-                    char buf[160];
-                    snprintf(buf, sizeof buf, "NOT GOOD RESTR INTER, i=%d, j=%d, best_ip=%d, best_jp=%d\n", i, j, best_ip, best_jp);
-                    throw BacktrackExit{0, buf};
-                }
-            } break;
-            case T_MULTI: {
-                f[i].type = T_MULTI;
-                f[j].type = T_MULTI;
-                const short *S = H.S;
-                const ccj_energy_params *P = H.P;
-                const int tt = H.pr(j, i);
-                int best_k = -1, best_row = -1, tmp = INF, mn = INF;
-                for (int k = i + 1; k <= j - 1; k++) {
-                    tmp = H.WM(i + 1, k - 1) + std::min(H.WMv(k, j - 1), H.WMp(k, j - 1)) + E_MLstem(P, tt, -1, -1) + P->MLclosing;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 1; }
-                    tmp = H.WM(i + 2, k - 1) + std::min(H.WMv(k, j - 1), H.WMp(k, j - 1)) + E_MLstem(P, tt, -1, S[i + 1]) + P->MLclosing + P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 2; }
-                    tmp = H.WM(i + 1, k - 1) + std::min(H.WMv(k, j - 2), H.WMp(k, j - 2)) + E_MLstem(P, tt, S[j - 1], -1) + P->MLclosing + P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 3; }
-                    tmp = H.WM(i + 2, k - 1) + std::min(H.WMv(k, j - 2), H.WMp(k, j - 2)) + E_MLstem(P, tt, S[j - 1], S[i + 1]) + P->MLclosing + 2 * P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 4; }
-                    tmp = (k - i - 1) * P->MLbase + H.WMp(k, j - 1) + E_MLstem(P, tt, -1, -1) + P->MLclosing;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 5; }
-                    if ((k - (i + 1) - 1) >= 0) tmp = (k - (i + 1) - 1) * P->MLbase + H.WMp(k, j - 1) + E_MLstem(P, tt, -1, S[i + 1]) + P->MLclosing + P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 6; }
-                    tmp = (k - i - 1) * P->MLbase + H.WMp(k, j - 2) + E_MLstem(P, tt, S[j - 1], -1) + P->MLclosing + P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 7; }
-                    if ((k - (i + 1) - 1) >= 0) tmp = (k - (i + 1) - 1) * P->MLbase + H.WMp(k, j - 2) + E_MLstem(P, tt, S[j - 1], S[i + 1]) + P->MLclosing + 2 * P->MLbase;
-                    if (tmp < mn) { mn = tmp; best_k = k; best_row = 8; }
-                }
-                switch (best_row) {
-                    case 1: push2(i + 1, best_k - 1, M_WM); push2(best_k, j - 1, M_WM); break;
-                    case 2: push2(i + 2, best_k - 1, M_WM); push2(best_k, j - 1, M_WM); break;
-                    case 3: push2(i + 1, best_k - 1, M_WM); push2(best_k, j - 2, M_WM); break;
-                    case 4: push2(i + 2, best_k - 1, M_WM); push2(best_k, j - 2, M_WM); break;
-                    case 5: push2(best_k, j - 1, M_WM); break;
-                    case 6: push2(best_k, j - 1, M_WM); break;
-                    case 7: push2(best_k, j - 2, M_WM); break;
-                    case 8: push2(best_k, j - 2, M_WM); break;
-                }
-            } break;
-        }
-    }
-
-    void bt_free(const Interval &cur) {
-        const int j = cur.j;
-        if (j == 1) return;
-        const short *S = H.S;
-        const int dangles = c->dangles;
-        int mn = INF, tmp = INF, acc = INF, eij = INF;
-        int best_row = -1, best_i = -1;
-        tmp = c->W[j - 1];
-        if (tmp < mn) { mn = tmp; best_row = 0; }
-        for (int i = 1; i <= j - 1; i++) {
-            acc = (i > 1) ? c->W[i - 1] : 0;
-            eij = H.V(i, j);
-            if (eij < INF) {
-                if (dangles == 2) {
-                    const int si1 = i > 1 ? S[i - 1] : -1;
-                    const int sj1 = j < n ? S[j + 1] : -1;
-                    tmp = eij + E_ExtLoop(H.P, H.pr(i, j), si1, sj1) + acc;
-                } else
-                    tmp = eij + E_ExtLoop(H.P, H.pr(i, j), -1, -1) + acc;
-                if (tmp < mn) { mn = tmp; best_i = i; best_row = 1; }
-            }
-            if (dangles == 1) {
-                eij = H.V(i + 1, j);
-                if (eij < INF) {
-                    tmp = eij + E_ExtLoop(H.P, H.pr(i + 1, j), S[i], -1) + acc;
-                    if (tmp < mn) { mn = tmp; best_i = i; best_row = 2; }
-                }
-                eij = H.V(i, j - 1);
-                if (eij < INF) {
-                    tmp = eij + E_ExtLoop(H.P, H.pr(i, j - 1), -1, S[j]) + acc;
-                    if (tmp < mn) { mn = tmp; best_i = i; best_row = 3; }
-                }
-                eij = H.V(i + 1, j - 1);
-                if (eij < INF) {
-                    tmp = eij + E_ExtLoop(H.P, H.pr(i + 1, j - 1), S[i], S[j]) + acc;
-                    if (tmp < mn) { mn = tmp; best_i = i; best_row = 4; }
-                }
+    // first strict minimum over candidates [0, count) in order
+    template <class F>
+    void scan(int count, F f, int &bv, int &bx) {
+        bv = bx = BIG;
+        for (int c = 0; c < count; ++c) {
+            const int t = f(c);
+            if (t < bv) {
+                bv = t;
+                bx = c;
             }
         }
-        for (int i = 1; i <= j - 1; i++) {
-            acc = (i - 1 > 0) ? c->W[i - 1] : 0;
-            eij = H.Pg(i, j);
-            if (eij < INF) {
-                tmp = eij + pe.PS + acc;
-                if (tmp < mn) { mn = tmp; best_row = 5; best_i = i; }
-            }
-            if (dangles == 1) {
-                eij = H.Pg(i + 1, j);
-                if (eij < INF) {
-                    tmp = eij + pe.PS + acc;
-                    if (tmp < mn) { mn = tmp; best_row = 6; best_i = i; }
-                }
-                eij = H.Pg(i, j - 1);
-                if (eij < INF) {
-                    tmp = eij + pe.PS + acc;
-                    if (tmp < mn) { mn = tmp; best_row = 7; best_i = i; }
-                }
-                eij = H.Pg(i + 1, j - 1);
-                if (eij < INF) {
-                    tmp = eij + pe.PS + acc;
-                    if (tmp < mn) { mn = tmp; best_row = 8; best_i = i; }
-                }
-            }
-        }
-        switch (best_row) {
-            case 0: push2(1, j - 1, FREE); break;
-            case 1: push2(best_i, j, LOOP); if (best_i - 1 > 1) push2(1, best_i - 1, FREE); break;
-            case 2: push2(best_i + 1, j, LOOP); if (best_i >= 1) push2(1, best_i, FREE); break;
-            case 3: push2(best_i, j - 1, LOOP); if (best_i - 1 > 1) push2(1, best_i - 1, FREE); break;
-            case 4: push2(best_i + 1, j - 1, LOOP); if (best_i >= 1) push2(1, best_i, FREE); break;
-            case 5: push2(best_i, j, P_P); if (best_i - 1 > 1) push2(1, best_i - 1, FREE); break;
-            case 6: push2(best_i + 1, j, P_P); if (best_i >= 1) push2(1, best_i, FREE); break;
-            case 7: push2(best_i, j - 1, P_P); if (best_i - 1 > 1) push2(1, best_i - 1, FREE); break;
-            case 8: push2(best_i + 1, j - 1, P_P); if (best_i >= 1) push2(1, best_i, FREE); break;
-        }
     }
-
-    void bt_wm(const Interval &cur) {
-        const int i = cur.i, j = cur.j;
-        const int MLb = H.P->MLbase;
-        int mn = H.WM(i, j - 1) + MLb;
-        int best_k = j, best_row = 5;
-        for (int k = i; k <= j - TURN - 1; k++) {
-            const int m1 = (k - i) * MLb + H.WMv(k, j);
-            if (m1 < mn) { mn = m1; best_k = k; best_row = 1; }
-            const int m2 = (k - i) * MLb + H.WMp(k, j);
-            if (m2 < mn) { mn = m2; best_k = k; best_row = 2; }
-            const int m3 = H.WM(i, k - 1) + H.WMv(k, j);
-            if (m3 < mn) { mn = m3; best_k = k; best_row = 3; }
-            const int m4 = H.WM(i, k - 1) + H.WMp(k, j);
-            if (m4 < mn) { mn = m4; best_k = k; best_row = 4; }
-        }
-        switch (best_row) {
-            case 1: push2(best_k, j, M_WMv); break;
-            case 2: push2(best_k, j, M_WMp); break;
-            case 3: push2(i, best_k - 1, M_WM); push2(best_k, j, M_WMv); break;
-            case 4: push2(i, best_k - 1, M_WM); push2(best_k + 1, j, M_WMp); break;  // A-B3
-            case 5: push2(i, j - 1, M_WM); break;
-        }
+    template <class F>
+    void scan2(int count, F f, int &fmin, int &bv, int &bx) {
+        fmin = BIG;
+        scan(count, [&](int c) {
+            const Int2 t = f(c);
+            fmin = std::min(fmin, t.y);
+            return t.x;
+        }, bv, bx);
     }
-
-    void bt_wmv(const Interval &cur) {
-        const int i = cur.i, j = cur.j;
-        const short *S = H.S;
-        const ccj_energy_params *P = H.P;
-        const int si = S[i], sj = S[j];
-        const int si1 = (i > 1) ? S[i - 1] : -1;
-        const int sj1 = (j < n) ? S[j + 1] : -1;
-        int tt = H.pr(i, j);
-        int mn = H.V(i, j) + ((c->dangles == 2) ? E_MLstem(P, tt, si1, sj1) : E_MLstem(P, tt, -1, -1));
-        int best_row = 1;
-        if (c->dangles == 1) {
-            tt = H.pr(i + 1, j);
-            int tmp = H.V(i + 1, j) + E_MLstem(P, tt, si, -1) + P->MLbase;
-            if (tmp < mn) { mn = tmp; best_row = 2; }
-            tt = H.pr(i, j - 1);
-            tmp = H.V(i, j - 1) + E_MLstem(P, tt, -1, sj) + P->MLbase;
-            if (tmp < mn) { mn = tmp; best_row = 3; }
-            tt = H.pr(i + 1, j - 1);
-            tmp = H.V(i + 1, j - 1) + E_MLstem(P, tt, si, sj) + 2 * P->MLbase;
-            if (tmp < mn) { mn = tmp; best_row = 4; }
-        }
-        const int tmp = H.WMv(i, j - 1) + P->MLbase;
-        if (tmp < mn) { mn = tmp; best_row = 5; }
-        switch (best_row) {
-            case 1: push2(i, j, LOOP); break;
-            case 2: push2(i + 1, j, LOOP); break;
-            case 3: push2(i, j - 1, LOOP); break;
-            case 4: push2(i + 1, j - 1, LOOP); break;
-            case 5: push2(i, j - 1, M_WMv); break;
-        }
+    void push(int i, int j, int k, int l, int type) { stk.push_back(Interval{i, j, k, l, type}); }
+    void setpair(int p, int q) {
+        f_pair[p] = q;
+        f_pair[q] = p;
     }
-
-    void bt_wmp(const Interval &cur) {
-        const int i = cur.i, j = cur.j;
-        int mn = H.Pg(i, j) + pe.PSM + pe.b;
-        int best_row = 1;
-        const int tmp = H.WMp(i, j - 1) + H.P->MLbase;
-        if (tmp < mn) { mn = tmp; best_row = 2; }
-        if (best_row == 2) push2(i, j - 1, M_WMp);  // case 1 commented out in reference (A-B2)
-    }
-
-    // ---------------------------------------------------------------------------------------
-    // pseudo_loop::backtrack, pseudo_loop.cc:861-2820
-    // ---------------------------------------------------------------------------------------
-    bool in_range4(int i, int j, int k, int l) const {
-        return !(i <= 0 || j <= 0 || k <= 0 || l <= 0 || i > n || j > n || k > n || l > n);
-    }
-
-    void pl_backtrack(const Interval &cur) {
-        const int PB = pe.PB, bp = pe.bp, cp = pe.cp, ap = pe.ap;
-        switch (cur.type) {
-            case P_P: {
-                const int i = cur.i, l = cur.j;
-                if (i >= l) die("border case: This should not have happened!, P_P");
-                int best_d = 0, best_j = 0, best_k = 0;
-                // first (j,d,k) in the reference's loop order whose sum equals the minimum P(i,l):
-                // k_pterm keeps it next to the minimum (Pk)
-                const int target = H.Pg(i, l);
-                if (l - i >= 3 && target < INF / 2) {
-                    const unsigned long long key = c->h_pk[c->a2(i, l)];
-                    const unsigned sig = (unsigned)(l - i), kk = (unsigned)(key & 0xffffffffull);
-                    best_j = i + (int)(kk / (sig * sig));
-                    best_d = i + (int)((kk / sig) % sig);
-                    best_k = i + (int)(kk % sig);
-                }
-                push4(i, best_k, best_j, best_d + 1, P_PK);
-                push4(best_j + 1, l, best_d, best_k + 1, P_PK);
-            } break;
-
-            case P_PK: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PK");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PK");
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = i + 1; d < j; ++d) {
-                    tmp = H.g4(PK, i, d, k, l) + H.WP(d + 1, j);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                }
-                for (int d = k + 1; d < l; ++d) {
-                    tmp = H.g4(PK, i, j, d, l) + H.WP(k, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.g4(PL, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 3; best_d = -1; }
-                tmp = H.g4(PM, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 4; best_d = -1; }
-                tmp = H.g4(PR, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 5; best_d = -1; }
-                tmp = H.g4(PO, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 6; best_d = -1; }
-                switch (best_row) {
-                    case 1: if (best_d > -1) { push4(i, l, best_d, k, P_PK); push2(best_d + 1, j, P_WP); } break;
-                    case 2: if (best_d > -1) { push4(i, l, j, best_d, P_PK); push2(k, best_d - 1, P_WP); } break;
-                    case 3: push4(i, l, j, k, P_PL); break;
-                    case 4: push4(i, l, j, k, P_PM); break;
-                    case 5: push4(i, l, j, k, P_PR); break;
-                    case 6: push4(i, l, j, k, P_PO); break;
-                }
-            } break;
-
-            case P_PL: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PL");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PL");
-                int mn = INF, tmp, best_row = -1;
-                if (H.pr(i, j) > 0) {
-                    tmp = get_PLiloop(i, j, k, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                    tmp = get_PXmloop(PLmloop10, PLmloop01, i + 1, j - 1, k, l, i, j, k, l) + bp; if (tmp < mn) { mn = tmp; best_row = 2; }
-                    if (j >= i + TURN + 1) { tmp = H.g4(PfromL, i + 1, j - 1, k, l); if (tmp < mn) { mn = tmp; best_row = 3; } }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PLiloop); break;
-                    case 2: push4(i, l, j, k, P_PLmloop); break;
-                    case 3:
-                        push4(i + 1, l, j - 1, k, P_PfromL);
-                        f[i].pair = j; f[j].pair = i; f[i].type = P_PL; f[j].type = P_PL;
-                        break;
-                }
-            } break;
-
-            case P_PR: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("boder cases: This should not have happened!, P_PR");
-                if (i < 0 || j < 0 || k < 0 || l < 0 || i >= n || j >= n || k >= n || l >= n)  // A-B5
-                    die("impossible cases: This should not have happened!, P_PR");
-                int mn = INF, tmp, best_row = -1;
-                if (H.pr(k, l) > 0) {
-                    tmp = get_PRiloop(i, j, k, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                    tmp = get_PXmloop(PRmloop10, PRmloop01, i, j, k + 1, l - 1, i, j, k, l) + bp; if (tmp < mn) { mn = tmp; best_row = 2; }
-                    if (l >= k + TURN + 1) { tmp = H.g4(PfromR, i, j, k + 1, l - 1); if (tmp < mn) { mn = tmp; best_row = 3; } }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PRiloop); break;
-                    case 2: push4(i, l, j, k, P_PRmloop); break;
-                    case 3:
-                        push4(i, l - 1, j, k + 1, P_PfromR);
-                        f[k].pair = l; f[l].pair = k; f[k].type = P_PR; f[l].type = P_PR;
-                        break;
-                }
-            } break;
-
-            case P_PM: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PM");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PM");
-                if (i == j && k == l) {
-                    f[j].pair = k; f[k].pair = j; f[j].type = P_PM; f[k].type = P_PM;
-                    return;
-                }
-                int mn = INF, tmp, best_row = -1;
-                if (H.pr(j, k) > 0) {
-                    tmp = get_PMiloop(i, j, k, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                    tmp = get_PXmloop(PMmloop10, PMmloop01, i, j - 1, k + 1, l, i, j, k, l) + bp; if (tmp < mn) { mn = tmp; best_row = 2; }
-                    if (k >= j + TURN - 1) { tmp = H.g4(PfromM, i, j - 1, k + 1, l); if (tmp < mn) { mn = tmp; best_row = 3; } }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PMiloop); break;
-                    case 2: push4(i, l, j, k, P_PMmloop); break;
-                    case 3:
-                        push4(i, l, j - 1, k + 1, P_PfromM);
-                        f[j].pair = k; f[k].pair = j; f[j].type = P_PM; f[k].type = P_PM;
-                        break;
-                }
-            } break;
-
-            case P_PO: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PO");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PO");
-                int mn = INF, tmp, best_row = -1;
-                if (H.pr(i, l) > 0) {
-                    tmp = get_POiloop(i, j, k, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                    tmp = get_PXmloop(POmloop10, POmloop01, i + 1, j, k, l - 1, i, j, k, l) + bp; if (tmp < mn) { mn = tmp; best_row = 2; }
-                    if (l >= i + TURN + 1) { tmp = H.g4(PfromO, i + 1, j, k, l - 1); if (tmp < mn) { mn = tmp; best_row = 3; } }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_POiloop); break;
-                    case 2: push4(i, l, j, k, P_POmloop); break;
-                    case 3:
-                        push4(i + 1, l - 1, j, k, P_PfromO);
-                        f[i].pair = l; f[l].pair = i; f[i].type = P_PO; f[l].type = P_PO;
-                        break;
-                }
-            } break;
-
-            case P_PfromL: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("This should not have happened!, P_PfromL");
-                if (!in_range4(i, j, k, l)) die("This should not have happened!, P_PfromL");
-                if (i == j && k == l) return;
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = i + 1; d < j; d++) {
-                    tmp = H.g4(PfromL, d, j, k, l) + H.WP(i, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                    tmp = H.g4(PfromL, i, d, k, l) + H.WP(d + 1, j);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.g4(PR, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 3; best_d = -1; }
-                tmp = H.g4(PM, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 4; best_d = -1; }
-                tmp = H.g4(PO, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 5; best_d = -1; }
-                switch (best_row) {
-                    case 1: if (best_d > -1) { push4(best_d, l, j, k, P_PfromL); push2(i, best_d - 1, P_WP); } break;
-                    case 2: if (best_d > -1) { push4(i, l, best_d, k, P_PfromL); push2(best_d + 1, j, P_WP); } break;
-                    case 3: push4(i, l, j, k, P_PR); break;
-                    case 4: push4(i, l, j, k, P_PM); break;
-                    case 5: push4(i, l, j, k, P_PO); break;
-                }
-            } break;
-
-            case P_PfromR: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("This should not have happened!, P_PfromR");
-                if (!in_range4(i, j, k, l)) die("impossible case: This should not have happened!, P_PfromR");
-                if (i == j && k == l) return;
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = k + 1; d < l; d++) {
-                    tmp = H.g4(PfromR, i, j, d, l) + H.WP(k, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                    tmp = H.g4(PfromR, i, j, k, d) + H.WP(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.g4(PM, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 3; best_d = -1; }
-                tmp = H.g4(PO, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 4; best_d = -1; }
-                switch (best_row) {
-                    case 1: if (best_d > -1) { push4(i, l, j, best_d, P_PfromR); push2(k, best_d - 1, P_WP); } break;
-                    case 2: if (best_d > -1) { push4(i, best_d, j, k, P_PfromR); push2(best_d + 1, l, P_WP); } break;
-                    case 3: push4(i, l, j, k, P_PM); break;
-                    case 4: push4(i, l, j, k, P_PO); break;
-                }
-            } break;
-
-            case P_PfromM: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("This should not have happened!, P_PfromM");
-                if (!in_range4(i, j, k, l)) die("This should not have happened!, P_PfromM");
-                if (i == j && k == l) return;
-                int mn = INF, tmp, best_d = -1;
-                for (int d = i + 1; d < j; d++) {
-                    tmp = H.g4(PfromMprime, i, d, k, l) + H.WP(d + 1, j);
-                    if (tmp < mn) { mn = tmp; best_d = d; }
-                }
-                if (best_d > -1) { push4(i, l, best_d, k, P_PfromMprime); push2(best_d + 1, j, P_WP); }
-            } break;
-
-            case P_PfromO: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PfromO");
-                if (!in_range4(i, j, k, l)) die("impossible case: This should not have happened!, P_PfromO");
-                if (i == j && k == l) return;
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = i + 1; d < j; d++) {
-                    tmp = H.g4(PfromO, d, j, k, l) + H.WP(i, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                }
-                for (int d = k + 1; d < l; d++) {
-                    tmp = H.g4(PfromO, i, j, k, d) + H.WP(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.g4(PL, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 3; best_d = -1; }
-                tmp = H.g4(PR, i, j, k, l) + PB; if (tmp < mn) { mn = tmp; best_row = 4; best_d = -1; }
-                switch (best_row) {
-                    case 1: if (best_d > -1) { push4(best_d, l, j, k, P_PfromO); push2(i, best_d - 1, P_WP); } break;
-                    case 2: if (best_d > -1) { push4(i, best_d, j, k, P_PfromO); push2(best_d + 1, l, P_WP); } break;
-                    case 3: push4(i, l, j, k, P_PL); break;
-                    case 4: push4(i, l, j, k, P_PR); break;
-                }
-            } break;
-
-            case P_WB: {
-                const int i = cur.i, l = cur.j;
-                if (i <= 0 || l <= 0 || i > n || l > n) die("impossible cases: This should not have happened!, P_WB");
-                if (i > l) return;
-                int mn = INF, tmp, best_row = -1;
-                tmp = H.WBPg(i, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                tmp = cp * (l - i + 1); if (tmp < mn) { mn = tmp; best_row = 2; }
-                if (best_row == 1) push2(i, l, P_WBP);
-            } break;
-
-            case P_WBP: {
-                const int i = cur.i, l = cur.j;
-                if (i > l) die("border case: This should not have happened!, P_WBP");
-                if (i <= 0 || l <= 0 || i > n || l > n) die("impossible cases: This should not have happened!, P_WBP");
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = i; d < l; d++) {
-                    tmp = H.WB(i, d - 1) + H.V(d, l) + bp + pe.PPS;
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                    tmp = H.WB(i, d - 1) + H.Pg(d, l) + pe.PSM + pe.PPS;
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.WBPg(i, l - 1) + cp;
-                if (tmp < mn) { mn = tmp; best_row = 3; }
-                switch (best_row) {
-                    case 1: push2(i, best_d - 1, P_WB); push2(best_d, l, LOOP); break;
-                    case 2: push2(i, best_d - 1, P_WB); push2(best_d, l, P_P); break;
-                    case 3: push2(i, l - 1, P_WBP); break;
-                }
-            } break;
-
-            case P_WP: {
-                const int i = cur.i, l = cur.j;
-                if (i <= 0 || l <= 0 || i > n || l > n) die("impossible cases: This should not have happened!, P_WP");
-                if (i > l) return;
-                int mn = INF, tmp, best_row = -1;
-                tmp = H.WPPg(i, l); if (tmp < mn) { mn = tmp; best_row = 1; }
-                tmp = pe.PUP * (l - i + 1); if (tmp < mn) { mn = tmp; best_row = 2; }
-                if (best_row == 1) push2(i, l, P_WPP);
-            } break;
-
-            case P_WPP: {
-                const int i = cur.i, l = cur.j;
-                if (i > l) die("border case: This should not have happened!, P_WPP");
-                if (i <= 0 || l <= 0 || i > n || l > n) die("impossible cases: This should not have happened!, P_WPP");
-                int mn = INF, tmp, best_row = -1, best_d = -1;
-                for (int d = i; d < l; d++) {
-                    tmp = H.WP(i, d - 1) + H.V(d, l) + 0 + pe.PPS;
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                    tmp = H.WP(i, d - 1) + H.Pg(d, l) + pe.PSP + pe.PPS;
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                tmp = H.WPPg(i, l - 1) + pe.PUP;
-                if (tmp < mn) { mn = tmp; best_row = 3; }
-                switch (best_row) {
-                    case 1: push2(i, best_d - 1, P_WP); push2(best_d, l, LOOP); break;
-                    case 2: push2(i, best_d - 1, P_WP); push2(best_d, l, P_P); break;
-                    case 3: push2(i, l - 1, P_WPP); break;
-                }
-            } break;
-
-            case P_PLiloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i < j && j < k - 1 && k < l)) die("border cases: This should not have happened!, P_PLiloop");
-                if (!in_range4(i, j, k, l)) die("impossbible cases: This should not have happened!, P_PLiloop");
-                f[i].pair = j; f[j].pair = i; f[i].type = P_PLiloop; f[j].type = P_PLiloop;
-                int mn = INF, tmp, best_row = -1, best_d = -1, best_dp = -1;
-                if (H.pr(i, j) > 0) {
-                    tmp = H.g4(PL, i + 1, j - 1, k, l) + H.e_stP(i, j);  // no i+TURN+2<j test here
-                    if (tmp < mn) { mn = tmp; best_row = 1; }
-                    const int max_d = std::min(j, i + MAXLOOP);
-                    for (int d = i + 1; d < max_d; ++d) {
-                        const int min_dp = std::max(d + TURN, j - MAXLOOP);
-                        for (int dp = j - 1; dp > min_dp; --dp) {  // no can_pair filter here
-                            tmp = H.e_intP(i, d, dp, j) + H.g4(PL, d, dp, k, l);
-                            if (tmp < mn) { mn = tmp; best_d = d; best_dp = dp; best_row = 2; }
-                        }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push4(i + 1, l, j - 1, k, P_PL); break;
-                    case 2: push4(best_d, l, best_dp, k, P_PL); break;
-                }
-            } break;
-
-            case P_PLmloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PLmloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PLmloop");
-                f[i].pair = j; f[j].pair = i; f[i].type = P_PLmloop; f[j].type = P_PLmloop;
-                const int br1 = H.g4(PLmloop10, i + 1, j - 1, k, l) + ap + bp;
-                const int br2 = H.g4(PLmloop01, i + 1, j - 1, k, l) + ap + bp;
-                if (br1 < br2) push4(i + 1, l, j - 1, k, P_PLmloop10);
-                else push4(i + 1, l, j - 1, k, P_PLmloop01);
-            } break;
-
-            case P_PLmloop00: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PLmloop00");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PLmloop00");
-                int mn = H.g4(PL, i, j, k, l) + bp, tmp;
-                int best_row = 1, best_d = -1;
-                for (int d = i; d <= j; ++d) {
-                    if (d > i) {
-                        tmp = H.WB(i, d - 1) + H.g4(PLmloop00, d, j, k, l);
-                        if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                    }
-                    if (d < j) {
-                        tmp = H.g4(PLmloop00, i, d, k, l) + H.WB(d + 1, j);
-                        if (tmp < mn) { mn = tmp; best_row = 3; best_d = d; }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PL); break;
-                    case 2: push4(best_d, l, j, k, P_PLmloop00); push2(i, best_d - 1, P_WB); break;
-                    case 3: push4(i, l, best_d, k, P_PLmloop00); push2(best_d + 1, j, P_WB); break;
-                }
-            } break;
-
-            case P_PLmloop01: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PLmloop01");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PLmloop01");
-                int mn = INF, tmp, best_d = -1;
-                for (int d = i; d < j; ++d) {
-                    tmp = H.g4(PLmloop00, i, d, k, l) + H.WBPg(d + 1, j);
-                    if (tmp < mn) { mn = tmp; best_d = d; }
-                }
-                push4(i, l, best_d, k, P_PLmloop00);
-                push2(best_d + 1, j, P_WBP);
-            } break;
-
-            case P_PLmloop10: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PLmloop10");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PLmloop10");
-                int mn = INF, tmp, best_d = -1, best_row = -1;
-                for (int d = i + 1; d <= j; ++d) {
-                    tmp = H.WBPg(i, d - 1) + H.g4(PLmloop00, d, j, k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                    if (d < j) {
-                        tmp = H.g4(PLmloop10, i, d, k, l) + H.WB(d + 1, j);
-                        if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push2(i, best_d - 1, P_WBP); push4(best_d, l, j, k, P_PLmloop00); break;
-                    case 2: push4(i, l, best_d, k, P_PLmloop10); push2(best_d + 1, j, P_WB); break;
-                }
-            } break;
-
-            case P_PRiloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PRiloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PRiloop");
-                f[k].pair = l; f[l].pair = k; f[k].type = P_PRiloop; f[l].type = P_PRiloop;
-                int mn = INF, tmp, best_row = -1, best_d = -1, best_dp = -1;
-                if (H.pr(k, l) > 0) {
-                    tmp = H.g4(PR, i, j, k + 1, l - 1) + H.e_stP(k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 1; }
-                    const int max_d = std::min(l, k + MAXLOOP);
-                    for (int d = k + 1; d < max_d; ++d) {
-                        const int min_dp = std::max(d + TURN, l - MAXLOOP);
-                        for (int dp = l - 1; dp > min_dp; --dp) {
-                            tmp = H.e_intP(k, d, dp, l) + H.g4(PR, i, j, d, dp);
-                            if (tmp < mn) { mn = tmp; best_d = d; best_dp = dp; best_row = 2; }
-                        }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l - 1, j, k + 1, P_PR); break;
-                    case 2: push4(i, best_dp, j, best_d, P_PR); break;
-                }
-            } break;
-
-            case P_PRmloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PRmloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PRmloop");
-                f[k].pair = l; f[l].pair = k; f[k].type = P_PRmloop; f[l].type = P_PRmloop;
-                const int br1 = H.g4(PRmloop10, i, j, k + 1, l - 1) + ap + bp;
-                const int br2 = H.g4(PRmloop01, i, j, k + 1, l - 1) + ap + bp;
-                if (br1 < br2) push4(i, l - 1, j, k + 1, P_PRmloop10);
-                else push4(i, l - 1, j, k + 1, P_PRmloop01);
-            } break;
-
-            case P_PRmloop00: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PRmloop00");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PRmloop00");
-                int mn = H.g4(PR, i, j, k, l) + bp, tmp;
-                int best_row = 1, best_d = -1;
-                for (int d = k; d <= l; ++d) {
-                    if (d > k) {
-                        tmp = H.WB(k, d - 1) + H.g4(PRmloop00, i, j, d, l);
-                        if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                    }
-                    if (d < l) {
-                        tmp = H.g4(PRmloop00, i, j, k, d) + H.WB(d + 1, l);
-                        if (tmp < mn) { mn = tmp; best_row = 3; best_d = d; }
-                    }
-                }
-                switch (best_row) {  // A-B4: (i,j,k,l) argument order
-                    case 1: push4(i, j, k, l, P_PR); break;
-                    case 2: push4(i, j, best_d, l, P_PRmloop00); push2(k, best_d - 1, P_WB); break;
-                    case 3: push4(i, j, k, best_d, P_PRmloop00); push2(best_d + 1, l, P_WB); break;
-                }
-            } break;
-
-            case P_PRmloop01: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PRmloop01");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PRmloop01");
-                int mn = H.g4(PRmloop01, i, j, k, l - 1) + cp, tmp;
-                int best_row = 1, best_d = -1;
-                for (int d = k; d < l; d++) {
-                    tmp = H.g4(PRmloop00, i, j, k, d) + H.WBPg(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l - 1, j, k, P_PRmloop01); break;
-                    case 2: push2(best_d + 1, l, P_WBP); push4(i, best_d, j, k, P_PRmloop00); break;
-                }
-            } break;
-
-            case P_PRmloop10: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PRmloop10");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PRmloop10");
-                int mn = H.g4(PRmloop10, i, j, k + 1, l) + cp, tmp;
-                int best_row = 1, best_d = -1;
-                for (int d = k + 1; d <= l; ++d) {
-                    tmp = H.WBPg(k, d - 1) + H.g4(PRmloop00, i, j, d, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k + 1, P_PRmloop10); break;
-                    case 2: push2(k, best_d - 1, P_WBP); push4(i, l, j, best_d, P_PRmloop00); break;
-                }
-            } break;
-
-            case P_PMiloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PMiloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PMiloop");
-                f[j].pair = k; f[k].pair = j; f[j].type = P_PMiloop; f[k].type = P_PMiloop;
-                int mn = INF, tmp, best_d = -1, best_dp = -1, best_row = -1;
-                if (H.pr(j, k) > 0) {
-                    tmp = H.g4(PM, i, j - 1, k + 1, l) + H.e_stP(j - 1, k + 1);
-                    if (tmp < mn) { mn = tmp; best_row = 1; }
-                    const int max_d = std::max(i, j - MAXLOOP);
-                    for (int d = j - 1; d > max_d; --d) {
-                        const int min_dp = std::min(l, k + MAXLOOP);
-                        for (int dp = k + 1; dp < min_dp; ++dp) {
-                            tmp = H.e_intP(d, j, k, dp) + H.g4(PM, i, d, dp, l);
-                            if (tmp < mn) { mn = tmp; best_d = d; best_dp = dp; best_row = 2; }
-                        }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j - 1, k + 1, P_PM); break;
-                    case 2: push4(i, l, best_d, best_dp, P_PM); break;
-                }
-            } break;
-
-            case P_PMmloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PMmloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PMmloop");
-                f[j].pair = k; f[k].pair = j; f[j].type = P_PMmloop; f[k].type = P_PMmloop;
-                const int br1 = H.g4(PMmloop10, i, j - 1, k + 1, l) + ap + bp;
-                const int br2 = H.g4(PMmloop01, i, j - 1, k + 1, l) + ap + bp;
-                if (br1 < br2) push4(i, l, j - 1, k + 1, P_PMmloop10);
-                else push4(i, l, j - 1, k + 1, P_PMmloop01);
-            } break;
-
-            case P_PMmloop00: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PMmloop00");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PMmloop00");
-                f[j].pair = k; f[k].pair = j; f[j].type = P_PMmloop; f[k].type = P_PMmloop;
-                int tmp, mn = H.g4(PM, i, j, k, l) + bp;
-                int best_row = 1, best_d = -1;
-                for (int d = i; d < j; ++d) {
-                    tmp = H.WB(d + 1, j) + H.g4(PMmloop00, i, d, k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                for (int d = k + 1; d <= l; d++) {
-                    tmp = H.g4(PMmloop00, i, j, d, l) + H.WB(k, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 3; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PM); break;
-                    case 2: push4(i, l, best_d, k, P_PMmloop00); push2(best_d + 1, j, P_WB); break;
-                    case 3: push4(i, l, j, best_d, P_PMmloop00); push2(k, best_d - 1, P_WB); break;
-                }
-            } break;
-
-            case P_PMmloop01: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PMmloop01");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PMmloop01");
-                int tmp, mn = H.g4(PMmloop01, i, j, k + 1, l) + cp;
-                int best_row = 1, best_d = -1;
-                for (int d = k + 1; d <= l; ++d) {
-                    tmp = H.g4(PMmloop00, i, j, d, l) + H.WBPg(k, d - 1);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k + 1, P_PMmloop01); break;
-                    case 2: push4(i, l, j, best_d, P_PMmloop00); push2(k, best_d - 1, P_WBP); break;
-                }
-            } break;
-
-            case P_PMmloop10: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_PMmloop10");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_PMmloop10");
-                int tmp, mn = H.g4(PMmloop10, i, j - 1, k, l) + cp;
-                int best_row = 1, best_d = -1;
-                for (int d = i + 1; d < j; ++d) {
-                    tmp = H.WBPg(d, j) + H.g4(PMmloop00, i, d - 1, k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j - 1, k, P_PMmloop10); break;
-                    case 2: push4(i, l, best_d - 1, k, P_PMmloop00); push2(best_d, j, P_WBP); break;
-                }
-            } break;
-
-            case P_POiloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_POiloop");
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_POiloop");
-                f[i].pair = l; f[l].pair = i; f[i].type = P_POiloop; f[l].type = P_POiloop;
-                int mn = INF, best_d = -1, best_dp = -1, best_row = -1;
-                if (H.pr(i, l) > 0) {
-                    const int tmp = H.g4(PO, i + 1, j, k, l - 1) + H.e_stP(i, l);
-                    if (tmp < mn) { mn = tmp; best_row = 1; }
-                    const int max_d = std::min(j, i + MAXLOOP);
-                    for (int d = i + 1; d < max_d; ++d) {
-                        const int min_dp = std::max(l - MAXLOOP, k);
-                        for (int dp = l - 1; dp > min_dp; --dp) {
-                            const int br2 = H.e_intP(i, d, dp, l) + H.g4(PO, d, j, dp, k);
-                            if (br2 < mn) { mn = br2; best_row = 2; best_d = d; best_dp = dp; }
-                        }
-                    }
-                }
-                switch (best_row) {
-                    case 1: push4(i + 1, l - 1, j, k, P_PO); break;
-                    case 2: push4(best_d, k, j, best_dp, P_PO); break;
-                }
-            } break;
-
-            case P_POmloop: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_POmloop");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_POmloop");
-                f[i].pair = l; f[l].pair = i; f[i].type = P_POmloop; f[l].type = P_POmloop;
-                const int br1 = H.g4(POmloop10, i + 1, j, k, l - 1) + ap + bp;
-                const int br2 = H.g4(POmloop01, i + 1, j, k, l - 1) + ap + bp;
-                if (br1 < br2) push4(i + 1, l - 1, j, k, P_POmloop10);
-                else push4(i + 1, l - 1, j, k, P_POmloop01);
-            } break;
-
-            case P_POmloop00: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_POmloop00");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_POmloop00");
-                int mn = H.g4(PO, i, j, k, l) + bp, tmp;
-                int best_row = 1, best_d = -1;
-                for (int d = i + 1; d <= j; ++d) {
-                    tmp = H.WB(i, d - 1) + H.g4(POmloop00, d, j, k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                for (int d = k; d < l; ++d) {
-                    tmp = H.g4(POmloop00, i, j, k, d) + H.WB(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_row = 3; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(i, l, j, k, P_PO); break;
-                    case 2: push4(best_d, l, j, k, P_POmloop00); push2(i, best_d - 1, P_WBP); break;  // sic
-                    case 3: push4(i, best_d, j, k, P_POmloop00); push2(best_d + 1, l, P_WB); break;
-                }
-            } break;
-
-            case P_POmloop01: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_POmloop01");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_POmloop01");
-                int mn = INF, tmp, best_d = -1;
-                for (int d = k; d < l; d++) {
-                    tmp = H.g4(POmloop00, i, j, k, d) + H.WBPg(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_d = d; }
-                }
-                push4(i, best_d, j, k, P_POmloop00);
-                push2(best_d + 1, l, P_WBP);
-            } break;
-
-            case P_POmloop10: {
-                const int i = cur.i, l = cur.j, j = cur.k, k = cur.l;
-                if (!(i <= j && j < k - 1 && k <= l)) die("border cases: This should not have happened!, P_POmloop10");
-                if (!in_range4(i, j, k, l)) die("impossible cases: This should not have happened!, P_POmloop10");
-                int mn = INF, tmp, best_d = -1, best_row = -1;
-                for (int d = i + 1; d <= j; ++d) {
-                    tmp = H.WBPg(i, d - 1) + H.g4(POmloop00, d, j, k, l);
-                    if (tmp < mn) { mn = tmp; best_row = 1; best_d = d; }
-                }
-                for (int d = k + 1; d < l; ++d) {
-                    tmp = H.g4(POmloop10, i, j, k, d) + H.WB(d + 1, l);
-                    if (tmp < mn) { mn = tmp; best_row = 2; best_d = d; }
-                }
-                switch (best_row) {
-                    case 1: push4(best_d, l, j, k, P_POmloop00); push2(i, best_d - 1, P_WBP); break;
-                    case 2: push4(i, best_d, j, k, P_POmloop10); push2(best_d + 1, l, P_WB); break;
-                }
-            } break;
-
-            default:
-                break;  // P_PLiloop5 etc.: no case in pseudo_loop::backtrack
-        }
-    }
-
-    // get_P?iloop (forward versions, with the can_pair filter), pseudo_loop.cc:682-808
-    int get_PLiloop(int i, int j, int k, int l) {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (!H.can_pair(i, j)) return INF;
-        int mn = INF;
-        if (i + TURN + 2 < j) mn = H.g4(PL, i + 1, j - 1, k, l) + H.e_stP(i, j);
-        const int max_d = std::min(j, i + MAXLOOP);
-        for (int d = i + 1; d < max_d; ++d) {
-            const int min_dp = std::max(d + TURN, j - MAXLOOP);
-            for (int dp = j - 1; dp > min_dp; --dp) {
-                if (!H.can_pair(d, dp)) continue;
-                mn = std::min(mn, H.e_intP(i, d, dp, j) + H.g4(PL, d, dp, k, l));
-            }
-        }
-        return mn;
-    }
-    int get_PRiloop(int i, int j, int k, int l) {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (!H.can_pair(k, l)) return INF;
-        int mn = INF;
-        if (k + TURN + 2 < l) mn = H.g4(PR, i, j, k + 1, l - 1) + H.e_stP(k, l);
-        const int max_d = std::min(l, k + MAXLOOP);
-        for (int d = k + 1; d < max_d; ++d) {
-            const int min_dp = std::max(d + TURN, l - MAXLOOP);
-            for (int dp = l - 1; dp > min_dp; --dp) {
-                if (!H.can_pair(d, dp)) continue;
-                mn = std::min(mn, H.e_intP(k, d, dp, l) + H.g4(PR, i, j, d, dp));
-            }
-        }
-        return mn;
-    }
-    int get_PMiloop(int i, int j, int k, int l) {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (!H.can_pair(j, k)) return INF;
-        int mn = INF;
-        if (i < j && k < l) mn = H.g4(PM, i, j - 1, k + 1, l) + H.e_stP(j - 1, k + 1);
-        const int max_d = std::max(i, j - MAXLOOP);
-        for (int d = j - 1; d > max_d; --d) {
-            const int min_dp = std::min(l, k + MAXLOOP);
-            for (int dp = k + 1; dp < min_dp; ++dp) {
-                if (!H.can_pair(d, dp)) continue;
-                mn = std::min(mn, H.e_intP(d, j, k, dp) + H.g4(PM, i, d, dp, l));
-            }
-        }
-        return mn;
-    }
-    int get_POiloop(int i, int j, int k, int l) {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        if (!H.can_pair(i, l)) return INF;
-        int mn = INF;
-        if (i < j && k < l) mn = H.g4(PO, i + 1, j, k, l - 1) + H.e_stP(i, l);
-        const int max_d = std::min(j, i + MAXLOOP);
-        for (int d = i + 1; d < max_d; ++d) {
-            const int min_dp = std::max(l - MAXLOOP, k);
-            for (int dp = l - 1; dp > min_dp; --dp) {
-                if (!H.can_pair(d, dp)) continue;
-                mn = std::min(mn, H.e_intP(i, d, dp, l) + H.g4(PO, d, j, dp, k));
-            }
-        }
-        return mn;
-    }
-    // get_P?mloop (pseudo_loop.cc:705-820): validity of the outer cell, then min of the two
-    int get_PXmloop(int m10, int m01, int i2, int j2, int k2, int l2, int i, int j, int k, int l) {
-        if (!(i <= j && j < k - 1 && k <= l)) return INF;
-        const int b1 = H.g4(m10, i2, j2, k2, l2) + pe.ap + pe.bp;
-        const int b2 = H.g4(m01, i2, j2, k2, l2) + pe.ap + pe.bp;
-        return std::min(b1, b2);
-    }
-
-    // W_final::fill_structure, W_final.cc:764-819
-    void fill_structure() {
-        struct Brack { char open, close; };
-        struct Band { char open, close; int outer_start, outer_end, inner_start, inner_end; };
-        std::stack<Brack> st;
-        st.push({'<', '>'});
-        st.push({'{', '}'});
-        st.push({'[', ']'});
-        st.push({'(', ')'});
-        std::list<Band> bands;
-        bands.push_back({'|', '|', 0, 0, 0, 0});
-        for (int i = 1; i <= n; i++) {
-            const int j = f[i].pair;
-            if (j == -1) {
-                structure[i] = '.';
-            } else if (i < j) {
-                bool inband = false;
-                for (auto it = bands.begin(); it != bands.end(); ++it) {
-                    if (i > it->inner_start && j < it->inner_end) {
-                        it->inner_start = i;
-                        it->inner_end = j;
-                        structure[i] = it->open;
-                        structure[j] = it->close;
-                        inband = true;
-                        break;
-                    }
-                }
-                if (!inband) {
-                    if (st.empty()) throw BacktrackExit{139, "CCJ: fill_structure: more than 4 crossing bands (reference pops an empty std::stack)\n"};
-                    Brack e = st.top();
-                    st.pop();
-                    bands.push_back({e.open, e.close, i, j, i, j});
-                    structure[i] = e.open;
-                    structure[j] = e.close;
-                }
-            } else {
-                for (auto it = bands.begin(); it != bands.end(); ++it) {
-                    if (i == it->outer_end) {
-                        st.push({it->open, it->close});
-                        break;
-                    }
-                }
-            }
-        }
+    void pairup(int p, int q, int type) {
+        setpair(p, q);
+        f_type[p] = f_type[q] = (int8_t)type;
     }
 };
+
+// W_final.cc:84-99: the driver loop, ended like the device's (k_backtrack)
+BtOut host_backtrack(const ccj_ctx *c, std::vector<int> &f_pair) {
+    const MirrorView H{HostStore(c)};
+    HostExec X{H, {}, std::vector<int>(c->n + 1, -1), std::vector<int8_t>(c->n + 1, (int8_t)T_NONE)};
+    Traceback<HostExec> B(X);
+    X.push(1, c->n, 0, 0, FREE);
+    while (!X.stk.empty() && X.st.status == BT_OK) {
+        if (X.st.steps >= BT_MAX_STEPS) {
+            X.st.status = BT_STEPS;
+            break;
+        }
+        const Interval cur = X.stk.back();
+        X.stk.pop_back();
+        ++X.st.steps;
+        B.node(cur);
+        if (H.bad) X.st.status = BT_ASSERT;
+    }
+    f_pair.swap(X.f_pair);
+    return X.st;
+}
+
+int bt_stack_cap(int n) { return std::min(4 * n + 64, 3000); }  // device node stack entries
+
+// The one way out of a traceback, device or host: the BtOut record as the reference's stdout lines
+// (appended to out), its stderr text (c->err) and the return code.
+int bt_exit(ccj_ctx *c, const BtOut &bo, std::string &out) {
+    for (int x = 0; x < bo.n_snbh; ++x) out += "Should not be here!\n";
+    switch (bo.status) {
+        case BT_OK: return CCJ_OK;
+        case BT_DIE:
+            c->err = std::string(bt_prefix(bo.prefix)) + "This should not have happened!, " + bt_case_name(bo.node) + "\n";
+            return CCJ_E_BACKTRACK;
+        case BT_INTER: {
+            char buf[160];
+            snprintf(buf, sizeof buf, "NOT GOOD RESTR INTER, i=%d, j=%d, best_ip=%d, best_jp=%d\n", bo.args[0], bo.args[1],
+                     bo.args[2], bo.args[3]);
+            c->err = buf;
+            return CCJ_E_INTER_EXIT;
+        }
+        case BT_ASSERT:
+            c->err = "CCJ: matrices.hh:167: Assertion `!(i<=0 || l> n_)' failed.\n";
+            return CCJ_E_BACKTRACK;
+        case BT_STEPS:
+            return set_err(c, CCJ_E_HIP, "%s traceback did not end within %d steps", c->host_tb ? "host" : "device", BT_MAX_STEPS);
+        default:
+            return set_err(c, CCJ_E_HIP, "device traceback stack overflow (capacity %d)", bt_stack_cap(c->n));
+    }
+}
+
+// W_final::fill_structure, W_final.cc:764-819: brackets from the pair list f[1..n] into
+// structure[1..n].  False when more than 4 bands cross (the reference pops an empty std::stack).
+bool fill_structure(int n, const int *f_pair, std::string &structure) {
+    struct Brack { char open, close; };
+    struct Band { char open, close; int outer_start, outer_end, inner_start, inner_end; };
+    std::stack<Brack> st;
+    st.push({'<', '>'});
+    st.push({'{', '}'});
+    st.push({'[', ']'});
+    st.push({'(', ')'});
+    std::list<Band> bands;
+    bands.push_back({'|', '|', 0, 0, 0, 0});
+    structure.assign(n + 1, '.');
+    for (int i = 1; i <= n; i++) {
+        const int j = f_pair[i];
+        if (j == -1) {
+            structure[i] = '.';
+        } else if (i < j) {
+            bool inband = false;
+            for (auto it = bands.begin(); it != bands.end(); ++it) {
+                if (i > it->inner_start && j < it->inner_end) {
+                    it->inner_start = i;
+                    it->inner_end = j;
+                    structure[i] = it->open;
+                    structure[j] = it->close;
+                    inband = true;
+                    break;
+                }
+            }
+            if (!inband) {
+                if (st.empty()) return false;
+                Brack e = st.top();
+                st.pop();
+                bands.push_back({e.open, e.close, i, j, i, j});
+                structure[i] = e.open;
+                structure[j] = e.close;
+            }
+        } else {
+            for (auto it = bands.begin(); it != bands.end(); ++it) {
+                if (i == it->outer_end) {
+                    st.push({it->open, it->close});
+                    break;
+                }
+            }
+        }
+    }
+    return true;
+}
+
+// bt_exit, then the brackets: what both executors' results go through
+int bt_finish(ccj_ctx *c, const BtOut &bo, const int *f_pair, std::string &structure, std::string &out) {
+    if (const int rc = bt_exit(c, bo, out)) return rc;
+    if (fill_structure(c->n, f_pair, structure)) return CCJ_OK;
+    c->err = "CCJ: fill_structure: more than 4 crossing bands (reference pops an empty std::stack)\n";
+    return CCJ_E_BACKTRACK;
+}
 
 uint64_t fnv(uint64_t h, const void *p, size_t nb) {
     const unsigned char *c = (const unsigned char *)p;
@@ -2552,8 +1593,7 @@ int result_enqueue(ccj_ctx *c) {
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_res, hipEventDisableTiming));
     }
     HIPCHK(c, (hipError_t)ccjk_compute_W(&c->T, c->d_W, c->d_wterm, c->st));
-    const int cap = std::min(4 * n + 64, 3000);
-    HIPCHK(c, (hipError_t)ccjk_backtrack(&c->T, c->d_W, c->d_fpair, c->d_ftype, c->d_btout, cap, c->st));
+    HIPCHK(c, (hipError_t)ccjk_backtrack(&c->T, c->d_W, c->d_fpair, c->d_ftype, c->d_btout, bt_stack_cap(n), c->st));
     HIPCHK(c, hipMemcpyAsync(c->hr_W, c->d_W, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->hr_fp, c->d_fpair, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->st));
     HIPCHK(c, hipMemcpyAsync(c->hr_ft, c->d_ftype, n + 1, hipMemcpyDeviceToHost, c->st));
@@ -2574,37 +1614,7 @@ int result_finish(ccj_ctx *c, std::string &structure, std::string &out, std::chr
     c->w_ms = 0;
     c->bt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->bt_steps = bo.steps;
-    const int cap = std::min(4 * n + 64, 3000);
-    for (int x = 0; x < bo.n_snbh; ++x) out += "Should not be here!\n";
-    switch (bo.status) {
-        case BT_OK: break;
-        case BT_DIE:
-            c->err = std::string(bt_prefix(bo.prefix)) + "This should not have happened!, " + bt_case_name(bo.node) + "\n";
-            return CCJ_E_BACKTRACK;
-        case BT_INTER: {
-            char buf[160];
-            snprintf(buf, sizeof buf, "NOT GOOD RESTR INTER, i=%d, j=%d, best_ip=%d, best_jp=%d\n", bo.args[0], bo.args[1],
-                     bo.args[2], bo.args[3]);
-            c->err = buf;
-            return CCJ_E_INTER_EXIT;
-        }
-        case BT_ASSERT:
-            c->err = "CCJ: matrices.hh:167: Assertion `!(i<=0 || l> n_)' failed.\n";
-            return CCJ_E_BACKTRACK;
-        case BT_STEPS:
-            return set_err(c, CCJ_E_HIP, "device traceback did not end within %d steps", BT_MAX_STEPS);
-        default:
-            return set_err(c, CCJ_E_HIP, "device traceback stack overflow (capacity %d)", cap);
-    }
-    HostView H(c);
-    Backtracker B(H, c);
-    for (int x = 1; x <= n; ++x) {
-        B.f[x].pair = c->hr_fp[x];
-        B.f[x].type = (char)c->hr_ft[x];
-    }
-    B.fill_structure();
-    structure = B.structure;
-    return CCJ_OK;
+    return bt_finish(c, bo, c->hr_fp, structure, out);
 }
 
 int device_result(ccj_ctx *c, std::string &structure, std::string &out) {
@@ -2644,18 +1654,11 @@ extern "C" int ccj_result(ccj_ctx *c, char *structure, double *energy_kcal, char
         compute_W(c);
         const auto t1 = std::chrono::steady_clock::now();
         c->w_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        HostView H(c);
-        Backtracker B(H, c);
-        try {
-            B.run();
-            B.fill_structure();
-        } catch (const BacktrackExit &e) {
-            c->err = e.stderr_msg;
-            rc = e.code == 0 ? CCJ_E_INTER_EXIT : e.code == 2 ? CCJ_E_HIP : CCJ_E_BACKTRACK;
-        }
+        std::vector<int> f_pair;
+        const BtOut bo = host_backtrack(c, f_pair);
+        c->bt_steps = bo.steps;
+        rc = bt_finish(c, bo, f_pair.data(), st, out);
         c->bt_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-        st = B.structure;
-        out = B.out;
     }
     return emit_result(c, rc, st, out, structure, energy_kcal, msgs, msgs_cap);
 }

@@ -77,7 +77,7 @@ typedef struct ccj_options {
     int shard_rank;
     int shard_simulate;  /* 1: run every shard's launches in this one context, no exchange (tests) */
     /* 0 (default): W and the traceback run on the GPU (no host copy of the 4-D matrices; getters
-     * copy them on first use).  1: on the host over the mirror (the reference restatement). */
+     * copy them on first use).  1: the same traceback logic run on the host over the mirror (tests). */
     int host_traceback;
     /* Level-kernel tuning (0 = default for both).
      * split_target: narrow late levels split each cell's split-point loops over up to 8 waves so

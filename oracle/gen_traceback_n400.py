@@ -4,8 +4,8 @@
 impossible-case exit only where it is expected, and pin the structure everywhere else).
 
 The oracle restatement (oracle/ccj_oracle.c) fills matrices but has no traceback, and a reference fold at
-n=400 takes ~12 h (its stock build aborts at n >= 214), so the outcome comes from the host restatement of
-the reference backtrack (ccj_host.cc Backtracker: W_final.cc:175-719 and pseudo_loop.cc:861-2820 in the
+n=400 takes ~12 h (its stock build aborts at n >= 214), so the outcome comes from the host executor of
+the traceback (ccj_traceback.h run by ccj_host.cc: W_final.cc:175-719 and pseudo_loop.cc:861-2820 in the
 reference's order, pinned against the reference's stdout / stderr / exit code on the 116 CLI goldens and
 the n <= 230 reference folds): W_final(..., host_traceback=True).  It runs over matrices whose 31 hashes
 and W(n) are first checked equal to tests/golden/hashes_n400.json, so the outcome is a function of the

@@ -121,7 +121,11 @@ def _result(wf):
 @pytest.mark.parametrize("seed", range(12))
 def test_device_traceback_equals_host_traceback(seed):
     """The GPU traceback (ccj_backtrack.hip, wave-parallel first-minimum scans) and the host
-    restatement over the mirror give the same MFE, brackets, stdout lines and exits."""
+    executor over the mirror give the same MFE, brackets, stdout lines and exits.  Both run the one
+    node logic of ccj_traceback.h, so this checks how the scans are executed (the parallel
+    lexicographic reduction against a sequential first strict minimum) and the two storage
+    adaptors, not the cases themselves: those are pinned against the reference's own runs in
+    tests/test_gpu_traceback_cases.py."""
     r = random.Random(7000 + seed)
     n = r.choice([24, 40, 64, 90, 130])
     seq = _rseq(9000 + seed, n, r.choice(["ACGU", "GGCCAU", "GCAU"]))
@@ -142,8 +146,8 @@ def test_device_traceback_equals_host_traceback(seed):
 @pytest.mark.parametrize("case", [c for c in E2E if len(c["seq"]) >= 30][:20],
                          ids=lambda c: f"n{len(c['seq'])}-{c['params']}-d{c['dangles']}-g{c['noGU']}")
 def test_host_traceback_matches_reference(case):
-    """The host restatement (mirror path) against the reference's CLI output, so both traceback
-    implementations stay pinned."""
+    """The host executor (mirror path) against the reference's CLI output, so both executors of the
+    traceback stay pinned."""
     wf = _wf(case["seq"], case["params"], case["dangles"], case["noGU"], host_traceback=True)
     try:
         wf.fill()

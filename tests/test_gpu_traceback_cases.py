@@ -7,7 +7,7 @@ reference itself printed:
     (the int16-saturated stack terms, the interior-loop precompute, the packed iloop entries);
   * the device traceback (k_backtrack): structure, energy, side messages, or the exit's stderr and
     code;
-  * the same through the host restatement (host_traceback=True);
+  * the same node logic (ccj_traceback.h) through the host executor (host_traceback=True);
   * the three largest cases band-sharded over an in-process world of 2.
 """
 import threading
