@@ -18,7 +18,8 @@ from typing import Optional
 
 __all__ = [
     "W_final", "ccj", "load_params", "load_par", "ParFileError", "param_path", "CCJError", "BacktrackExit", "lib", "MAT4", "MAT2",
-    "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2",
+    "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
+    "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2",
     "SampleExit", "pf_exp_hashes", "load_pfraw",
 ]
 
@@ -94,6 +95,20 @@ class _Options(ctypes.Structure):
                 ("split_target", ctypes.c_int), ("share_splits", ctypes.c_int)]
 
 COMM_ID_BYTES = 128
+DEFAULT_SPLIT_TARGET = 9216  # ccj_host.cc create_impl (include/ccj.h ccj_options.split_target)
+
+
+class LevelSchedule(tuple):
+    """One level's launch regime for one rank (include/ccj.h ccj_level_schedule): sharing (bool),
+    split (k_level4d: 1/2/4/8, 0 = no block), lead_split (k_level4d_lead: 2/4/8, 0 = no leader
+    launch), g_lo, g_hi (the sharing range)."""
+    __slots__ = ()
+    sharing = property(lambda s: s[0])
+    split = property(lambda s: s[1])
+    lead_split = property(lambda s: s[2])
+    g_lo = property(lambda s: s[3])
+    g_hi = property(lambda s: s[4])
+    regime = property(lambda s: (s[1], s[2]))
 
 
 _lib = None
@@ -161,6 +176,10 @@ def lib() -> ctypes.CDLL:
     L.ccj_comm_init_local.restype = ip
     L.ccj_level_layout.argtypes = [ip, ip, ip, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ip)]
     L.ccj_level_layout.restype = ip
+    L.ccj_level_schedule.argtypes = [ip, ip, ip, ip, ip, ip, ctypes.POINTER(ip)]
+    L.ccj_level_schedule.restype = ip
+    L.ccj_ctx_level_schedule.argtypes = [vp, ip, ip, ctypes.POINTER(ip)]
+    L.ccj_ctx_level_schedule.restype = ip
     L.ccj_params_load_par.argtypes = [cp, cp, cp, cp, ip]
     L.ccj_params_load_par.restype = ip
     L.ccj_params_load_par_string.argtypes = [cp, cp, cp, cp, ip]
@@ -428,6 +447,20 @@ class W_final:
         self._check(lib().ccj_hashes(self._h, out))
         return {name: "%016x" % out[x] for x, name in enumerate(HASH_NAMES)}
 
+    def level_schedule(self, t: int, rank: int = -1) -> LevelSchedule:
+        """The launch regime this context runs level t in (include/ccj.h ccj_ctx_level_schedule),
+        from the split target and share flag it resolved (options and environment); rank: another
+        rank's launches in a shard_simulate context (default: this context's own)."""
+        out = (ctypes.c_int * 7)()
+        self._check(lib().ccj_ctx_level_schedule(self._h, t, rank, out))
+        return LevelSchedule((bool(out[0]), out[1], out[2], out[3], out[4]))
+
+    def schedule_options(self):
+        """(split_target, share) as this context resolved them (0 = never split)."""
+        out = (ctypes.c_int * 7)()
+        self._check(lib().ccj_ctx_level_schedule(self._h, 0, -1, out))
+        return out[5], bool(out[6])
+
     def set_timing(self, mode: int) -> None:
         """What later ccj() calls time: 0 = the fill; 1 (default) = + level durations; 2 = + per-kernel
         family times (k_diag2d, k_iloop) from extra marker events, which slow the fill down."""
@@ -509,6 +542,17 @@ def level_layout(n: int, t: int, world: int):
     if rc != CCJ_OK:
         raise CCJError(rc, "bad layout arguments")
     return C.value, M.value
+
+
+def level_schedule(n: int, t: int, world: int = 1, rank: int = 0, split_target: int = DEFAULT_SPLIT_TARGET,
+                   share: bool = True) -> LevelSchedule:
+    """The launch regime of level t for one rank (no GPU needed; include/ccj.h ccj_level_schedule).
+    split_target is the resolved target: 0 = never split (what the option's -1 means)."""
+    out = (ctypes.c_int * 5)()
+    rc = lib().ccj_level_schedule(n, t, world, rank, split_target, 1 if share else 0, out)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "bad schedule arguments")
+    return LevelSchedule((bool(out[0]), out[1], out[2], out[3], out[4]))
 
 
 def ccj(seq: str, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False,

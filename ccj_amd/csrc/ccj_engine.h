@@ -281,6 +281,83 @@ inline int64_t cell_offset_host(const LevelDesc &L, int x, int a, int h, int i) 
     return (int64_t)mslot(x) * L.C + (int64_t)a * L.M + (int64_t)h * L.m - (int64_t)h * (h - 1) / 2 + (i - 1);
 }
 
+// ---- the level schedule: which launch regime level t runs in (host only) ----
+// create_impl, ccjk_level4d and ccjk_level4d_lead all take it from here; ccj_level_schedule /
+// ccj_ctx_level_schedule (include/ccj.h) export it.
+
+// narrow levels: split each chunk's a/b loops over up to 8 waves so ~split_target waves run at once
+inline int sched_level_split(int n, int t, int nblk, int split_target) {
+    const int m = n - t - 2;
+    if (m <= 0 || nblk <= 0) return 1;
+    const long waves = (long)nblk * ((m * (m + 1) / 2 + 63) / 64);
+    int split = 1;
+    while (split_target > 0 && split < 8 && waves * split * 2 <= split_target) split *= 2;
+    return split;
+}
+
+// The sharing range [g_lo, g_hi): from the first level that runs unsplit (by the whole level's
+// block count, whatever the world) to the last level; empty (0, 0) with sharing off or when every
+// level splits.  The narrow early levels keep their split loops (short scans); on the narrow late
+// levels k_level4d_lead splits the long scans like the level heuristic would.  (Sharing on the
+// unsplit middle levels only measured 0.6 ms slower at n=200.)
+inline void sched_share_range(int n, int split_target, bool share, int &g_lo, int &g_hi) {
+    g_lo = g_hi = 0;
+    if (!share) return;
+    const int nlev = n > 2 ? n - 2 : 0;
+    for (int t = 0; t < nlev; ++t)
+        if (sched_level_split(n, t, t + 1, split_target) == 1) {
+            g_lo = t;
+            g_hi = nlev;
+            return;
+        }
+}
+
+// Does k_level4d_lead run a-block a of sharing level t (a leader or a full scan on either side;
+// the roles of level4d_body)?  cost: its scan cost, a leader step at about 2.5 plain steps.  A
+// follower whose leader would lie below g_lo (t - ra < g_lo) has none and scans its full range.
+inline bool sched_lead_block(int t, int a, int g_lo, double *cost) {
+    const int b = t - a, ra = a % SHARE_R, rb = b % SHARE_R;
+    const int ar = b >= SHARE_R - 1 ? (ra == 0 ? 1 : (t - ra >= g_lo ? 2 : 0)) : 0;
+    const int br = a >= SHARE_R - 1 ? (rb == 0 ? 1 : (t - rb >= g_lo ? 2 : 0)) : 0;
+    if (ar == 2 && br == 2) return false;
+    if (cost) *cost = (ar == 1 ? 2.5 : 1.0) * (ar == 2 ? ra : a) + (br == 1 ? 2.5 : 1.0) * (br == 2 ? rb : b);
+    return true;
+}
+
+// rank r's blocks of level t that k_level4d_lead runs (the length of its lord list)
+inline int sched_lead_count(int t, int G, int r, int g_lo, int g_hi) {
+    if (t < g_lo || t >= g_hi) return 0;
+    int cnt = 0;
+    for (int a = 0; a <= t; ++a) cnt += shard_owner(a, G) == r && sched_lead_block(t, a, g_lo, nullptr);
+    return cnt;
+}
+
+struct LevelSched {
+    int sharing;     // 1: t in [g_lo, g_hi)
+    int split;       // k_level4d's split for rank r's blocks (1 on the sharing levels; 0: no launch)
+    int lead_split;  // k_level4d_lead's waves per chunk (0: rank r launches no leader block)
+};
+
+// lead_nblk: the length of rank r's lord list at t (< 0: count it)
+inline LevelSched level_sched(int n, int t, int G, int r, int split_target, int g_lo, int g_hi, int lead_nblk) {
+    LevelSched s{0, 0, 0};
+    if (n - t - 2 <= 0 || t < 0) return s;
+    s.sharing = t >= g_lo && t < g_hi;
+    const int own = shard_count(t, G, r);
+    // on the sharing levels the plain launch only has follower cells (short scans): never split
+    if (own > 0) s.split = s.sharing ? 1 : sched_level_split(n, t, own, split_target);
+    if (!s.sharing) return s;
+    if (lead_nblk < 0) lead_nblk = sched_lead_count(t, G, r, g_lo, g_hi);
+    if (lead_nblk <= 0) return s;
+    // each leader chunk's scans are split over lead_split waves of one workgroup (the barriers
+    // inside the leader scans need every wave of the workgroup on the same chunk)
+    constexpr int lsplit = 2;  // 1 / 3 / 4 measured +1.1 / +6.5 / +9.4 ms
+    // narrow late levels: as many split waves as the plain heuristic would give the rank's blocks
+    const int sp = sched_level_split(n, t, own, split_target);
+    s.lead_split = sp > lsplit ? sp : lsplit;
+    return s;
+}
+
 }  // namespace ccj
 
 // Kernel launchers (ccj_kernels.hip); all return a hipError_t as int.

@@ -861,24 +861,9 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     // and its followers run one cell per lane) and the partial-record ring
     int g_lo = 0, g_hi = 0;
     long long accC = 0;
-    if (c->share) {
-        // from the first level that runs unsplit to the last level: the narrow early levels keep
-        // their split loops (short scans); on the narrow late levels k_level4d_lead splits the long
-        // scans like the level heuristic would (ccjk_level4d_lead).  (Sharing on the unsplit middle
-        // levels only measured 0.6 ms slower at n=200.)
-        g_lo = -1;
-        for (int t = 0; t < c->nlev && g_lo < 0; ++t)
-            if (ccjk_level_split(n, t, t + 1, c->split_target) == 1) g_lo = t;
-        if (g_lo < 0) {
-            g_hi = g_lo < 0 ? 0 : g_lo;
-            for (int t = std::max(g_lo, 0); g_lo >= 0 && t < c->nlev; ++t)
-                if (ccjk_level_split(n, t, t + 1, c->split_target) == 1 && g_hi == t) g_hi = t + 1;
-            if (g_lo < 0) g_lo = 0;
-        } else {
-            g_hi = c->nlev;
-        }
-        for (int t = g_lo; t < g_hi; ++t) accC = std::max<long long>(accC, c->lv_host[t].C);
-    }
+    // from the first level that runs unsplit to the last level (sched_share_range, ccj_engine.h)
+    sched_share_range(n, c->split_target, c->share, g_lo, g_hi);
+    for (int t = g_lo; t < g_hi; ++t) accC = std::max<long long>(accC, c->lv_host[t].C);
     if (g_hi > g_lo) {
         // the a-blocks k_level4d_lead runs on each sharing level (a leader or a full scan on either
         // side; the roles of level4d_body), ordered by scan cost, longest first, so the longest
@@ -894,12 +879,8 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
             if (t < g_lo || t >= g_hi) continue;
             blk.clear();
             for (int a = 0; a <= t; ++a) {
-                if (shard_owner(a, G) != r) continue;
-                const int b = t - a, ra = a % SHARE_R, rb = b % SHARE_R;
-                const int ar = b >= SHARE_R - 1 ? (ra == 0 ? 1 : (t - ra >= g_lo ? 2 : 0)) : 0;
-                const int br = a >= SHARE_R - 1 ? (rb == 0 ? 1 : (t - rb >= g_lo ? 2 : 0)) : 0;
-                if (ar == 2 && br == 2) continue;
-                const double cost = (ar == 1 ? 2.5 : 1.0) * (ar == 2 ? ra : a) + (br == 1 ? 2.5 : 1.0) * (br == 2 ? rb : b);
+                double cost = 0;
+                if (shard_owner(a, G) != r || !sched_lead_block(t, a, g_lo, &cost)) continue;
                 blk.push_back({cost, a});
             }
             std::stable_sort(blk.begin(), blk.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
@@ -1964,6 +1945,32 @@ extern "C" int ccj_shard_blocks(int n, int t, int world, int rank, int *a_out, i
     const int cnt = shard_count(t, world, rank);
     for (int o = 0; o < cnt && o < cap; ++o) a_out[o] = shard_a(o, world, rank);
     return cnt;
+}
+
+// The launch regime of level t for one rank (ccj_engine.h level_sched: what create_impl,
+// ccjk_level4d and ccjk_level4d_lead use), without a context ...
+extern "C" int ccj_level_schedule(int n, int t, int world, int rank, int split_target, int share, int *out5) {
+    if (!out5 || n < 1 || world < 1 || rank < 0 || rank >= world || t < 0 || split_target < 0) return CCJ_E_ARG;
+    int g_lo, g_hi;
+    sched_share_range(n, split_target, share != 0, g_lo, g_hi);
+    const LevelSched s = level_sched(n, t, world, rank, split_target, g_lo, g_hi, -1);
+    out5[0] = s.sharing, out5[1] = s.split, out5[2] = s.lead_split, out5[3] = g_lo, out5[4] = g_hi;
+    return CCJ_OK;
+}
+
+// ... and of a live context: the range it created its lists for, the leader list it launches from
+extern "C" int ccj_ctx_level_schedule(const ccj_ctx *c, int t, int rank, int *out7) {
+    if (!c || !out7 || t < 0) return CCJ_E_ARG;
+    if (rank < 0) rank = c->rank;
+    if (rank >= c->world || (!c->simulate && rank != c->rank)) return CCJ_E_ARG;
+    const int G = c->world, g_lo = c->T.g_lo, g_hi = c->T.g_hi;
+    int lead_nblk = 0;
+    if (t >= g_lo && t < g_hi)
+        lead_nblk = c->lord_off.empty() ? shard_count(t, G, rank) : c->lord_off[(size_t)t * G + rank + 1] - c->lord_off[(size_t)t * G + rank];
+    const LevelSched s = level_sched(c->n, t, G, rank, c->split_target, g_lo, g_hi, lead_nblk);
+    out7[0] = s.sharing, out7[1] = s.split, out7[2] = s.lead_split, out7[3] = g_lo, out7[4] = g_hi;
+    out7[5] = c->split_target, out7[6] = c->share ? 1 : 0;
+    return CCJ_OK;
 }
 
 extern "C" int ccj_level_layout(int n, int t, int world, long long *C, int *M) {

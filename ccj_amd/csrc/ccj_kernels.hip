@@ -2235,13 +2235,9 @@ extern "C" int ccjk_canon(const DevTables *T, int x, const long long *offij, int
 }
 
 // narrow levels: split each chunk's a/b loops over up to 8 waves so ~split_target waves run at once
+// (the level schedule, ccj_engine.h)
 extern "C" int ccjk_level_split(int n, int t, int nblk, int split_target) {
-    const int m = n - t - 2;
-    if (m <= 0 || nblk <= 0) return 1;
-    const long waves = (long)nblk * ((m * (m + 1) / 2 + 63) / 64);
-    int split = 1;
-    while (split_target > 0 && split < 8 && waves * split * 2 <= split_target) split *= 2;
-    return split;
+    return sched_level_split(n, t, nblk, split_target);
 }
 
 extern "C" int ccjk_level4d(const DevTables *T, int t, int G, int rank, int copies, void *stream) {
@@ -2253,7 +2249,7 @@ extern "C" int ccjk_level4d(const DevTables *T, int t, int G, int rank, int copi
     if (nblk <= 0) return 0;
     const long waves = (long)nblk * wavesPerA;
     // on the sharing levels this launch only has follower cells (short scans): never split
-    const int split = (t >= T->g_lo && t < T->g_hi) ? 1 : ccjk_level_split(T->n, t, nblk, T->split_target);
+    const int split = level_sched(T->n, t, G, rank, T->split_target, T->g_lo, T->g_hi, 0).split;
     const int threads = split <= 4 ? 256 : 64 * split;
     const int cpb = threads / 64 / split;
     const long blocks = (waves + cpb - 1) / cpb;
@@ -2274,11 +2270,9 @@ extern "C" int ccjk_level4d_lead(const DevTables *T, int t, int G, int rank, voi
     const int nblk = T->lord ? T->lord_off_h[t * G + rank + 1] - T->lord_off_h[t * G + rank] : own;
     if (nblk <= 0) return 0;
     const long waves = (long)nblk * wavesPerA;
-    // each leader chunk's scans are split over `split` waves of one workgroup (the barriers inside
-    // the leader scans need every wave of the workgroup on the same chunk)
-    constexpr int lsplit = 2;  // 1 / 3 / 4 measured +1.1 / +6.5 / +9.4 ms
-    // narrow late levels: as many split waves as the plain heuristic would give the rank's blocks
-    const int sp = imax(lsplit, ccjk_level_split(T->n, t, own, T->split_target));
+    // each leader chunk's scans are split over sp waves of one workgroup: 2, or on the narrow late
+    // levels as many as the plain heuristic would give the rank's blocks (level_sched, ccj_engine.h)
+    const int sp = level_sched(T->n, t, G, rank, T->split_target, T->g_lo, T->g_hi, nblk).lead_split;
     const size_t shmem = sp > 1 ? (size_t)(sp - 1) * (LEAD_RED > 22 ? LEAD_RED : 22) * 64 * sizeof(int) : 0;
     hipLaunchKernelGGL(k_level4d_lead, dim3((unsigned)waves), dim3(64 * sp), shmem, (hipStream_t)stream, *T, t, wavesPerA,
                        sp, G, rank, nblk, 1);

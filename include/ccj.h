@@ -80,8 +80,11 @@ typedef struct ccj_options {
      * copy them on first use).  1: the same traceback logic run on the host over the mirror (tests). */
     int host_traceback;
     /* Level-kernel tuning (0 = default for both).
-     * split_target: narrow late levels split each cell's split-point loops over up to 8 waves so
-     *   about this many waves run at once (default 9216); < 0 never splits.
+     * split_target: narrow levels split each cell's split-point loops over up to 8 waves so
+     *   about this many waves run at once (default 9216); < 0 never splits.  It also places the
+     *   sharing range: from the first level that runs unsplit to the last.  Under the default
+     *   no level runs unsplit below n = 159, so smaller folds share nothing; small targets
+     *   reproduce every regime at small n (ccj_level_schedule below; tests/test_schedule.py).
      * share_splits: split-point sharing between the cells of one gap column: a
      *   leader cell scans its whole split range once for itself and the next CCJ_SHARE_R-1 cells of
      *   its column; < 0 turns it off (every cell scans its own range). */
@@ -183,6 +186,22 @@ int  ccj_comm_init(ccj_ctx *ctx, const char *id);
 int  ccj_shard_blocks(int n, int t, int world, int rank, int *a_out, int cap);
 /* Per-matrix element count C_t of level t and the a-block size M_t (the same for every world). */
 int  ccj_level_layout(int n, int t, int world, long long *C, int *M);
+/* The launch regime of level t for one rank (host helper, no GPU), from the one
+ * schedule function the launches themselves use.  split_target: the resolved target (0 = never
+ * split, what ccj_options.split_target < 0 resolves to); share: 0 = sharing off.
+ * out5 = {sharing (1: t in [g_lo, g_hi)),
+ *         k_level4d's split for the rank's blocks: 1, 2, 4 or 8 (0: the rank has no block at t),
+ *         k_level4d_lead's waves per chunk: 2, 4 or 8 (0: the rank launches no leader block at t),
+ *         g_lo, g_hi}.
+ * Levels [g_lo, g_hi) share (0, 0: none); followers on g_lo .. g_lo+2 whose leader would lie
+ * below g_lo scan their full range in the leader launch.  CCJ_E_ARG on bad arguments; a level
+ * without cells (t > n-3) gives zeros with the range. */
+int  ccj_level_schedule(int n, int t, int world, int rank, int split_target, int share, int *out5);
+/* The same for a live context, with the target and share flag it resolved from its options and
+ * the environment (CCJ_SPLIT_TARGET, CCJ_SHARE_SPLITS) and the leader lists it launches from:
+ * out7 = the five values above, then {resolved split_target, share (0/1)}.  rank < 0: the
+ * context's own rank; another rank only in a shard_simulate context. */
+int  ccj_ctx_level_schedule(const ccj_ctx *ctx, int t, int rank, int *out7);
 /* The level-t exchange is two all-gathers: part 0 ("edge") = each rank's blocks
  * a % 4 == 3, the only cells of level t another rank's level t+1 reads, then its P(t+1) partials
  * (4(n+1) elements) and span t (20(n+1) elements), on the level stream; part 1 ("bulk") = the other

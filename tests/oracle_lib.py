@@ -114,6 +114,57 @@ class OracleFold:
         self.close()
 
 
+def first_difference(get4_got, get4_want, n, names):
+    """Walk the 4-D matrices `names` level by level (t = a + b ascending, the order the fill computes
+    them in; then a-block a = j - i, then i, then k) and return the first cell at which
+    get4_got(x, i, j, k, l) differs from get4_want(...): {"matrix", "cell": (i, j, k, l), "t", "a",
+    "got", "want"}, or None.  Failure reports only (two calls per cell): n <= 72."""
+    xs = [(HASH_NAMES.index(nm), nm) for nm in names if nm in HASH_NAMES[:22]]
+    for t in range(max(n - 2, 0)):
+        for a in range(t + 1):
+            b = t - a
+            for i in range(1, n + 1):
+                j = i + a
+                for k in range(j + 2, n - b + 1):
+                    l = k + b
+                    for x, nm in xs:
+                        g, w = get4_got(x, i, j, k, l), get4_want(x, i, j, k, l)
+                        if g != w:
+                            return {"matrix": nm, "cell": (i, j, k, l), "t": t, "a": a, "got": g, "want": w}
+    return None
+
+
+def explain_mismatch(wf, seq, params, dangles, noGU, bad, world=1, simulate=True):
+    """Text for a failed hash comparison of the context wf: the first differing cell of the
+    differing 4-D matrices against OracleFold, with the launch regime wf ran that level in (its
+    schedule getter; band-sharded: the regime of the rank that owns the cell's a-block, or this
+    rank's own outside shard_simulate); differing 2-D matrices are named with their first
+    differing (i, j)."""
+    n = len(seq)
+    if n > 72:
+        return f"matrices differ: {bad}"
+    o = OracleFold(seq, blob(params), dangles, noGU)
+    try:
+        out = [f"matrices differ: {bad}"]
+        d = first_difference(wf.get4, o.get4, n, bad)
+        if d:
+            rank = (d["a"] // 4) % world if world > 1 and simulate else -1
+            s = wf.level_schedule(d["t"], rank)
+            out.append("first differing 4-D cell: %s(i=%d, j=%d, k=%d, l=%d) level t=%d a=%d: got %d, oracle %d; "
+                       "level regime%s: sharing=%s plain split %d lead split %d, g_lo=%d g_hi=%d"
+                       % (d["matrix"], *d["cell"], d["t"], d["a"], d["got"], d["want"],
+                          " of rank %d" % rank if rank >= 0 else "", s.sharing, s.split, s.lead_split, s.g_lo, s.g_hi))
+        for nm in bad:
+            if nm in HASH_NAMES[22:30]:
+                x = HASH_NAMES.index(nm) - 22
+                cell = next(((i, j) for w in range(n) for i in range(1, n - w + 1) for j in [i + w]
+                             if wf.get2(x, i, j) != o.get2(x, i, j)), None)
+                out.append(f"first differing {nm}(i, j) by span: {cell}")
+        return "\n".join(out)
+    finally:
+        o.close()
+
+
 def golden(name):
     with open(os.path.join(GOLDEN, name)) as f:
         return json.load(f)

@@ -32,6 +32,28 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_level_schedule_symbols():
+    """The schedule helper and the context getter (include/ccj.h) are declared, exported and mirrored
+    in ccj_amd; the helper answers without a GPU and the getter refuses a NULL context."""
+    import ccj_amd
+    assert {"ccj_level_schedule", "ccj_ctx_level_schedule"} <= declared_symbols()
+    L = ctypes.CDLL(LIB)
+    ip = ctypes.c_int
+    L.ccj_level_schedule.argtypes = [ip] * 6 + [ctypes.POINTER(ip)]
+    out = (ip * 5)()
+    assert L.ccj_level_schedule(55, 11, 1, 0, 352, 1, out) == 0
+    assert list(out) == [1, 1, 2, 11, 53]
+    assert L.ccj_level_schedule(55, 10, 1, 0, 352, 1, out) == 0
+    assert list(out) == [0, 2, 0, 11, 53]
+    assert L.ccj_level_schedule(55, 10, 1, 0, 352, 1, None) == 1  # CCJ_E_ARG
+    L.ccj_ctx_level_schedule.argtypes = [ctypes.c_void_p, ip, ip, ctypes.POINTER(ip)]
+    out7 = (ip * 7)()
+    assert L.ccj_ctx_level_schedule(None, 0, -1, out7) == 1
+    s = ccj_amd.level_schedule(55, 11, split_target=352)
+    assert tuple(s) == (True, 1, 2, 11, 53) and s.regime == (1, 2)
+    assert hasattr(ccj_amd.W_final, "level_schedule")
+
+
 def test_num_cells():
     L = ctypes.CDLL(LIB)
     L.ccj_num_cells.restype = ctypes.c_uint64

@@ -8,6 +8,9 @@ with CCJ_E_STATE if either disagrees with the GPU's count; CCJ_HOST_COUNT=1 size
 the host count alone.  The switches are read once per process, so each mode runs in a child
 interpreter that folds reference cases (unsharded and band-sharded in one context) and prints every
 matrix hash; the parent compares them with the reference's (tests/golden/hashes_large.json).
+The child also reports the schedule its contexts resolved (target, g_lo, regimes):
+tests/test_gpu_schedule.py runs both modes once more with CCJ_SPLIT_TARGET in the child's
+environment, where the n = 100 / 150 cases here share nothing.
 """
 import json
 import os
@@ -34,7 +37,9 @@ for case in json.loads(sys.argv[2]):
         wf = W_final(case["seq"], case["dangles"], params=case["params"], noGU=bool(case["noGU"]), **kw)
         try:
             e = wf.ccj()
-            out.append({"tag": case["tag"], "world": world, "hashes": wf.hashes(), "line": f"{wf.structure} ({e:g})"})
+            sch = [wf.level_schedule(t, r) for r in range(world) for t in range(wf.n - 2)]
+            out.append({"tag": case["tag"], "world": world, "hashes": wf.hashes(), "line": f"{wf.structure} ({e:g})",
+                        "target": wf.schedule_options()[0], "g_lo": sch[0].g_lo, "regimes": sorted({s.regime for s in sch})})
         finally:
             wf.close()
 print(json.dumps(out))

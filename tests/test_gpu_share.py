@@ -2,9 +2,14 @@
 
 A leader cell scans its whole split range for itself and the next SHARE_R-1 cells of each of its
 gap columns; the followers scan only the split points the leader did not see.  Min is
-order-independent, so the fill must stay bit-identical to the reference.  By default sharing
-covers the unsplit middle levels (n >= ~60); split_target=-1 turns level splitting off so that
-sharing covers every level, which exercises leaders, followers and the ring at small n.
+order-independent, so the fill must stay bit-identical to the reference.  By default (split
+target 9216) sharing covers the levels from the first one that runs unsplit to the last, and no
+level runs unsplit below n = 159: at smaller n the default schedule shares nothing.
+split_target=-1 turns level splitting off so that sharing covers every level (g_lo = 0, lead
+split 2), which exercises leaders, followers and the ring at small n; the other regimes (lead
+splits 4 and 8, g_lo > 0 and its leaderless followers, the split plain launches below g_lo) are
+reached at n = 52 .. 64 by tests/test_gpu_schedule.py, and tests/test_schedule.py pins which n and
+targets reach what.
 """
 import random
 
@@ -20,10 +25,12 @@ def _rseq(seed, n, alphabet="ACGU"):
     return "".join(r.choice(alphabet) for _ in range(n))
 
 
-def _hashes(seq, params, d=2, g=0, **kw):
+def _hashes(seq, params, d=2, g=0, probe=None, **kw):
     from ccj_amd import W_final
     wf = W_final(seq, d, params=params, noGU=bool(g), **kw)
     try:
+        if probe is not None:
+            probe(wf)
         wf.fill()
         try:
             wf.result()
@@ -57,13 +64,32 @@ def test_sharing_random_inputs_match_oracle(seed):
         o.close()
 
 
-@pytest.mark.parametrize("n,seed", [(90, 1), (140, 2)])
+@pytest.mark.parametrize("n,seed", [(90, 1), (140, 2), (168, 3)])
 def test_sharing_on_off_identical(n, seed):
-    """Default schedule (sharing on the unsplit levels) == sharing off == sharing everywhere."""
+    """Default schedule == sharing off == sharing everywhere.  At n = 90 and 140 the default schedule
+    shares nothing (it is the share-off schedule: every level splits); n = 168 is a little above the
+    smallest n whose default schedule shares (159), with all three lead splits and g_lo > 0; the
+    context's schedule getter says which is which."""
     seq = _rseq(seed, n)
-    h_on = _hashes(seq, "Turner04")
-    assert _hashes(seq, "Turner04", share_splits=-1) == h_on
-    assert _hashes(seq, "Turner04", split_target=-1) == h_on
+    seen = {}
+
+    def probe(key):
+        def f(wf):
+            seen[key] = [wf.level_schedule(t) for t in range(n - 2)]
+        return f
+
+    h_on = _hashes(seq, "Turner04", probe=probe("default"))
+    assert _hashes(seq, "Turner04", share_splits=-1, probe=probe("off")) == h_on
+    assert _hashes(seq, "Turner04", split_target=-1, probe=probe("everywhere")) == h_on
+    assert not any(s.sharing or s.lead_split for s in seen["off"])
+    assert all(s.regime == (1, 2) for s in seen["everywhere"])
+    if n >= 159:
+        g_lo = seen["default"][0].g_lo
+        assert 0 < g_lo and seen["default"][0].g_hi == n - 2
+        assert {s.lead_split for s in seen["default"][g_lo:]} == {2, 4, 8}
+        assert all(s.split > 1 and not s.sharing for s in seen["default"][:g_lo])
+    else:
+        assert seen["default"] == seen["off"]
 
 
 def test_sharing_n400_same_result():
