@@ -49,6 +49,7 @@ struct DevStore {
     }
     __device__ __forceinline__ int Vtype(int i, int j) const { return T.Vt[(j - i) * rs + i]; }
     __device__ __forceinline__ int raw4(int x, int i, int j, int k, int l) const {
+        if (tab_only(x)) return tab_get(T, x, i, j, k, l);  // PL / PR multiloop family: 2-D table (ccj_mloop2d.h)
         const int t = (j - i) + (l - k), m = n - t - 2, h = k - j - 2, a = j - i;
         const LvlDev L = ld[t];
         const long long cell = (long long)a * L.M + h * m - ((h * (h - 1)) >> 1) + i - 1;

@@ -16,13 +16,16 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "ccj_energy.h"  // Mat4, Penalties
+#include "ccj_mloop2d.h"  // the six table-carried matrices
 #include "ccj_params.h"
 
 namespace ccj {
 
-// The matrices the loop records carry (below), which d4 does not store unless DevTables::mat5: the 5
-// no fill kernel reads back as matrices and 6 more the level kernel's stack terms read from the
-// records (rec_get); d4 stores the other 11.
+// The matrices d4 does not store unless DevTables::mat5: those the loop records carry (below; the 5
+// no fill kernel reads back as matrices and the ones the level kernel's stack terms read from the
+// records, rec_get) and, of the six table-carried matrices (ccj_mloop2d.h), PLmloop00, PLmloop10 and
+// PRmloop00.  The other three table-carried ones (PLmloop01, PRmloop01, PRmloop10) keep their stored
+// slots, which the fill does not write: slot order (mslot) is the host mirror's and stays.
 constexpr unsigned REC_MASK = (1u << PfromL) | (1u << PfromR) | (1u << PfromMprime) | (1u << PfromO) | (1u << PLmloop00) |
                               (1u << PLmloop10) | (1u << PRmloop00) | (1u << PMmloop00) | (1u << PMmloop10) |
                               (1u << POmloop00) | (1u << POmloop10);
@@ -68,16 +71,19 @@ struct LvlDev {     // per-level descriptor read by the level kernel (one s_load
 };
 
 // AoS loop records: the operands the fused split-point loops of k_level4d read at
-// one neighbour cell, int16 fields packed in one record, so each neighbour costs one dwordx4 (dwordx3)
-// load instead of 5-7 int16 loads.  Three record types per level, each indexed like a matrix
-// (a*M + G(h) + i-1): RA and RL (16 bytes) in T.rec, level t at ld[t].lr (RA: C records, then RL),
-// RK (12 bytes) in T.rk at ld[t].lr / 2:
-//   RA (a-loop, both sides): PLmloop00 PMmloop00 | POmloop00 PfromL | PfromO PLmloop10 | PfromMprime PK
-//   RK (b-loop, k side):     PRmloop00 PMmloop00 | PfromR min(PL,PR) | PK -
-//   RL (b-loop, l side):     PRmloop00 PMmloop00 | POmloop00 PMmloop10 | POmloop10 PfromR | PfromO -
-// Values are the stored (clamped) int16 matrix values; unused slots hold 32767.
-enum RecType { RA = 0, RL = 1, NREC = 2 };  // 16-byte record types in T.rec (RK lives in T.rk)
-static_assert(sizeof(uint3) == 12, "RK records are 12 bytes");
+// one neighbour cell, int16 fields packed in one record, so each neighbour costs one dwordx3 (dwordx2)
+// load instead of 4-6 int16 loads.  Three record types per level, each indexed like a matrix
+// (a*M + G(h) + i-1): RA and RL (12 bytes) in T.rec, level t at ld[t].lr (RA: C records, then RL),
+// RK (8 bytes) in T.rk at ld[t].lr / 2:
+//   RA (a-loop, both sides): PMmloop00 POmloop00 | PfromL PfromO | PfromMprime PK
+//   RK (b-loop, k side):     PMmloop00 PfromR | min(PL,PR) PK
+//   RL (b-loop, l side):     PMmloop00 POmloop00 | PMmloop10 POmloop10 | PfromR PfromO
+// Values are the stored (clamped) int16 matrix values.  (The PL / PR multiloop families are not in
+// the records: they are 2-D tables, ccj_mloop2d.h.)
+enum RecType { RA = 0, RL = 1, NREC = 2 };  // 12-byte record types in T.rec (RK lives in T.rk)
+typedef uint3 rec_t;  // RA, RL
+typedef uint2 rk_t;   // RK
+static_assert(sizeof(rec_t) == 12 && sizeof(rk_t) == 8, "record sizes");
 
 // Split-point sharing (k_level4d).  The cells of one gap column — same (j,k,l)
 // for the i-side split, (i,k,l) j-side, (i,j,l) k-side, (i,j,k) l-side — sit on consecutive levels
@@ -86,14 +92,13 @@ static_assert(sizeof(uint3) == 12, "RK records are 12 bytes");
 // range once and also reduces it for the next SHARE_R-1 cells of each of its columns; those
 // followers scan only the split points the leader did not see and take the rest from a partial
 // record.  Partial records live in a ring of SHARE_R level slots (the level t' cells' records are
-// written at levels t'-SHARE_R+1 .. t'-1 and read at t'), SHARE_NACC 16-byte records per cell:
-//   AI (i side): PLmloop00 PLmloop10 | PMmloop10 POmloop00 | POmloop10 PfromL | PfromO -
-//   AJ (j side): PLmloop00 PLmloop01 | PMmloop00 PLmloop10 | PfromL PfromMprime | PK -
-//   AK (k side): PRmloop00 PRmloop10 | PMmloop00 PfromR | PfromM'' PK | PfromO(l side) -
-//   AL (l side): PRmloop00 PRmloop01 | PMmloop01 POmloop00 | POmloop01 PMmloop10 | POmloop10 PfromR
-// (AK's 7th slot carries the l side's 9th field; it is written by the l-side leader, the first six
-// by the k-side leader, so the two never write the same bytes.)  Values are min-clamped at 32767
-// like a store (clamp commutes with min).  The leader's W(i-r, .) / W(., j+r) operands are read
+// written at levels t'-SHARE_R+1 .. t'-1 and read at t'), SHARE_NACC 16-byte slots per cell, of which
+// a record uses its first 12 / 8 / 8 / 16 bytes:
+//   AI (i side, 12 B): PMmloop10 POmloop00 | POmloop10 PfromL | PfromO -
+//   AJ (j side,  8 B): PMmloop00 PfromL | PfromMprime PK
+//   AK (k side,  8 B): PMmloop00 PfromR | PfromM'' PK
+//   AL (l side, 16 B): PMmloop01 POmloop00 | POmloop01 PMmloop10 | POmloop10 PfromR | PfromO -
+// Values are min-clamped at 32767 like a store (clamp commutes with min).  The leader's W(i-r, .) / W(., j+r) operands are read
 // from the span-major WBW pairs (span s-1+r, coalesced along the lanes).
 #ifndef CCJ_SHARE_R
 #define CCJ_SHARE_R 4
@@ -212,9 +217,13 @@ struct DevTables {
     int16_t *d4;                   // 4-D storage base
     const long long *lb;           // element offset of level t in d4
     const LvlDev *ld;             // per-level descriptors
-    uint4 *rec;                    // AoS loop records RA, RL: level t at ld[t].lr
+    rec_t *rec;                    // AoS loop records RA, RL: level t at ld[t].lr
     long long nrec;                // records allocated (debug bounds checks)
-    uint3 *rk;                     // RK records: level t at ld[t].lr / 2 (nrec / 2 of them)
+    rk_t *rk;                      // RK records: level t at ld[t].lr / 2 (nrec / 2 of them)
+    // the PL / PR multiloop families (ccj_mloop2d.h): six int16 tables [w][p], row stride rs, one
+    // after another (tab_index) tabN elements apart; span w is written by k_diag2d(w)
+    int16_t *tab;
+    long long tabN;
     // interior-loop copies of PL / PR / PM, laid out so that the lanes of one k_iloop wave share
     // the loop's closing pair:
     //   PLx(t,a,h,i) = lbx + a*M + G(i-1) + h               (h fastest: fixed (i,j), lanes k)
@@ -248,32 +257,34 @@ struct DevTables {
     long long accC;
 };
 
-// The record-carried matrices (rec_only) live only in the loop records (RA / RK / RL), unless
-// DevTables::mat5: the level kernel skips their d4 stores and d4 has no slots for them.
-// rec_get reads one from the records of the cell at in-level offset cell (a*M + G(h) + i-1); k_mat5
-// writes a level's eleven into a scratch buffer for the host mirror.
+// The record-carried matrices (rec_only and not tab_only) live only in the loop records (RA / RK /
+// RL), unless DevTables::mat5: the level kernel skips their d4 stores and d4 has no slots for them
+// (DESIGN.md §3).  rec_get reads one from the records of the cell at in-level offset cell (a*M + G(h)
+// + i-1); k_mat5 writes a level's into a scratch buffer for the host mirror.
 __device__ __forceinline__ int rlo16(unsigned w) { return (int)(int16_t)(w & 0xffffu); }
 __device__ __forceinline__ int rhi16(unsigned w) { return (int)(int16_t)(w >> 16); }
 __device__ __forceinline__ int rec_get(const DevTables &T, int x, const LvlDev &L, long long cell) {
-    const uint4 *rp = T.rec + L.lr;
-    if (x == PRmloop00 || x == PfromR) {  // RK: Rm00|Mm00, fR|PLR, K|-
-        const uint3 r = T.rk[(L.lr >> 1) + cell];
-        return x == PRmloop00 ? rlo16(r.x) : rlo16(r.y);
+    const rec_t *rp = T.rec + L.lr;
+    if (x == PfromR) return rhi16(T.rk[(L.lr >> 1) + cell].x);  // RK: Mm00|fR, PLR|K
+    if (x == PMmloop10 || x == POmloop10) {  // RL: Mm00|Om00, Mm10|Om10, fR|fO
+        const rec_t r = rp[(long long)L.C + cell];
+        return x == PMmloop10 ? rlo16(r.y) : rhi16(r.y);
     }
-    if (x == PMmloop10 || x == POmloop10) {  // RL: Rm00|Mm00, Om00|Mm10, Om10|fR, fO|-
-        const uint4 r = rp[(long long)L.C + cell];
-        return x == PMmloop10 ? rhi16(r.y) : rlo16(r.z);
-    }
-    const uint4 r = rp[cell];  // RA: Lm00|Mm00, Om00|fL, fO|Lm10, fMp|K
+    const rec_t r = rp[cell];  // RA: Mm00|Om00, fL|fO, fMp|K
     switch (x) {
-        case PLmloop00: return rlo16(r.x);
-        case PMmloop00: return rhi16(r.x);
-        case POmloop00: return rlo16(r.y);
-        case PfromL: return rhi16(r.y);
-        case PfromO: return rlo16(r.z);
-        case PLmloop10: return rhi16(r.z);
-        default: return rlo16(r.w);  // PfromMprime
+        case PMmloop00: return rlo16(r.x);
+        case POmloop00: return rhi16(r.x);
+        case PfromL: return rlo16(r.y);
+        case PfromO: return rhi16(r.y);
+        default: return rlo16(r.z);  // PfromMprime
     }
+}
+// A table-carried matrix (tab_only, ccj_mloop2d.h) at cell (i,j,k,l): every reader outside the fill
+// takes the six from here, whatever d4 holds.
+__device__ __forceinline__ int tab_get(const DevTables &T, int x, int i, int j, int k, int l) {
+    const int ti = tab_index(x);
+    const int w = ti < 3 ? j - i : l - k, p = ti < 3 ? i : k;
+    return (int)T.tab[(long long)ti * T.tabN + w * T.rs + p];
 }
 
 // element offset of cell (a,h,i) of matrix x inside level t of the host mirror (relative to lv_offh[t])
@@ -383,4 +394,5 @@ int ccjk_items(const ccj::DevTables *T, int G, int rank, int simulate, long long
                uint32_t *items, int pass, void *stream);
 int ccjk_canon(const ccj::DevTables *T, int x, const long long *offij, int16_t *out, void *stream);
 int ccjk_mat5(const ccj::DevTables *T, int t, int16_t *out, void *stream);
+int ccjk_tab_slots(const ccj::DevTables *T, int t, int16_t *out_st, int16_t *out_rec, void *stream);
 }

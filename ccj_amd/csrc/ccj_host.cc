@@ -137,8 +137,9 @@ struct ccj_ctx {
     LvlDev *d_ld = nullptr;
     int16_t *d4x = nullptr, *pmx = nullptr;  // interior-loop copies of PL/PR and PM (IT_PAD into the allocations)
     int16_t *d4x_alloc = nullptr, *pmx_alloc = nullptr;
-    uint4 *d_rec = nullptr;                  // AoS loop records RA, RL (16 bytes)
-    uint3 *d_rk = nullptr;                   // AoS loop records RK (12 bytes)
+    rec_t *d_rec = nullptr;                  // AoS loop records RA, RL (12 bytes)
+    rk_t *d_rk = nullptr;                    // AoS loop records RK (8 bytes)
+    int16_t *d_tab = nullptr;                // the six PL / PR multiloop tables [w][p] (ccj_mloop2d.h)
     uint4 *d_acc = nullptr;                  // partial-record ring (split-point sharing)
     int16_t *d_lord = nullptr;               // long-scan a-blocks per sharing level, longest first
     int *d_lord_off = nullptr;
@@ -851,12 +852,12 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     const size_t ie_elems = (size_t)(n + 1) * c->rs;  // the u1 = u2 = 0 plane (k_build_il evaluates the rest)
     if (c->total4 > 0 && hipMalloc(&c->d4, (size_t)c->total4 * sizeof(int16_t)) != hipSuccess)
         return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for 4-D matrices failed", c->total4 * 2e-9);
-    // AoS loop records: NREC 16-byte records per cell (ccj_engine.h)
+    // AoS loop records: NREC 12-byte records and one 8-byte RK record per cell (ccj_engine.h)
     c->nrec = c->ncell * NREC;
-    if (c->nrec > 0 && (hipMalloc(&c->d_rec, (size_t)c->nrec * sizeof(uint4)) != hipSuccess ||
-                        hipMalloc(&c->d_rk, (size_t)c->ncell * sizeof(uint3)) != hipSuccess))
+    if (c->nrec > 0 && (hipMalloc(&c->d_rec, (size_t)c->nrec * sizeof(rec_t)) != hipSuccess ||
+                        hipMalloc(&c->d_rk, (size_t)c->ncell * sizeof(rk_t)) != hipSuccess))
         return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for loop records failed",
-                       c->nrec * 16e-9 + c->ncell * 12e-9);
+                       c->nrec * 12e-9 + c->ncell * 8e-9);
     // split-point sharing: the level range it covers (every level of it runs unsplit, so each leader
     // and its followers run one cell per lane) and the partial-record ring
     int g_lo = 0, g_hi = 0;
@@ -961,6 +962,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     }
     HIPCHK(cp, hipMalloc(&c->d2i, A2_N * plane * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_wbw, plane * sizeof(int2)));
+    HIPCHK(cp, hipMalloc(&c->d_tab, 6 * plane * sizeof(int16_t)));  // k_init2d resets them with every fill
     HIPCHK(cp, hipMalloc(&c->d_pk, plane * sizeof(unsigned long long)));
     HIPCHK(cp, hipMalloc(&c->d_W, (n + 1) * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_wterm, plane * sizeof(int)));
@@ -1037,6 +1039,8 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.d4x = c->d4x;
     T.rec = c->d_rec;
     T.rk = c->d_rk;
+    T.tab = c->d_tab;
+    T.tabN = (long long)plane;
     T.nrec = c->nrec;
     T.pmx = c->pmx;
     T.nx = c->nx;
@@ -1171,14 +1175,8 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     // exchange is unpacked (bulk_done[t]; lev_done[t] then only covers the rank's own cells and the
     // other ranks' edge blocks, which is all level t+1 reads of level t)
     const std::vector<hipEvent_t> &lvl_full = xchg ? c->bulk_done : c->lev_done;
-    // what follows a level's completion on this rank: P terms pushed by it, the host-mirror copy
+    // what follows a level's completion on this rank: the P terms pushed by it
     auto after_level = [&](int s) -> int {
-        if (c->overlap && c->h4) {
-            // stream the finished level to the pinned host mirror while later levels run
-            HIPCHK(c, hipStreamWaitEvent(c->st_copy, lvl_full[s], 0));
-            const size_t bytes = (size_t)NMAT4 * c->lv_host[s].C * sizeof(int16_t);
-            HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], c->d4 + c->lv_off[s], bytes, hipMemcpyDeviceToHost, c->st_copy));
-        }
         // P(s+3) only needs PK levels <= s; band-sharded, this rank's partials are combined in the
         // bulk exchange of level s+1, which then records p_done[s+3]
         if (s + 3 < n) {
@@ -1366,6 +1364,19 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     if (getenv("CCJ_TRACE_ENQUEUE"))
         fprintf(stderr, "ccj_fill_device: enqueue %.2f ms\n",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - enq0).count());
+    if (c->overlap && c->h4) {
+        // stream each finished level to the pinned host mirror while later levels run.  Its six
+        // table-carried slots (ccj_mloop2d.h) are written first, from table spans <= s (k_diag2d(s));
+        // enqueued here because every event st_copy waits on must have been recorded
+        for (int s = 0; s < c->nlev; ++s) {
+            HIPCHK(c, hipStreamWaitEvent(c->st_copy, lvl_full[s], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->st_copy, c->dg_done[s], 0));
+            int16_t *lv = c->d4 + c->lv_off[s];
+            HIPCHK(c, (hipError_t)ccjk_tab_slots(&c->T, s, lv, lv + (size_t)NMAT_ST * c->lv_host[s].C, c->st_copy));
+            const size_t bytes = (size_t)NMAT4 * c->lv_host[s].C * sizeof(int16_t);
+            HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], lv, bytes, hipMemcpyDeviceToHost, c->st_copy));
+        }
+    }
     // join: the fill ends when the last level (every rank's part of it) and the last span are done
     HIPCHK(c, hipStreamWaitEvent(st, c->dg_done[n - 1], 0));
     if (xchg && c->nlev >= 1) HIPCHK(c, hipStreamWaitEvent(st, c->bulk_done[c->nlev - 1], 0));
@@ -1504,7 +1515,12 @@ extern "C" int ccj_sync_host(ccj_ctx *c) {
         const size_t hbytes = (size_t)NMAT4 * c->ncell * sizeof(int16_t);
         if (!c->h4 && hipHostMalloc(&c->h4, hbytes, hipHostMallocDefault) != hipSuccess)
             return set_err(c, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", hbytes * 1e-9);
-        if (c->mat5) {  // d4 has the mirror's layout
+        if (c->mat5) {  // d4 has the mirror's layout; the fill left the six table-carried slots unwritten
+            for (int t = 0; t < c->nlev; ++t) {
+                int16_t *lv = c->d4 + c->lv_off[t];
+                HIPCHK(c, (hipError_t)ccjk_tab_slots(&c->T, t, lv, lv + (size_t)NMAT_ST * c->lv_host[t].C, c->st));
+            }
+            HIPCHK(c, hipStreamSynchronize(c->st));
             HIPCHK(c, hipMemcpy(c->h4, c->d4, hbytes, hipMemcpyDeviceToHost));
         } else {  // per level: the NMAT_ST stored slots, then the record-carried ones read back from the records
             size_t cmax = 0;
@@ -1515,9 +1531,12 @@ extern "C" int ccj_sync_host(ccj_ctx *c) {
             int rc = CCJ_OK;
             for (int t = 0; t < c->nlev && rc == CCJ_OK; ++t) {
                 const size_t C = (size_t)c->lv_host[t].C;
-                if (hipMemcpy(c->h4 + c->lv_offh[t], c->d4 + c->lv_off[t], (size_t)NMAT_ST * C * sizeof(int16_t),
+                // the six table-carried matrices: three into their (otherwise unwritten) stored slots of
+                // d4, three into the scratch beside the record-carried ones
+                if (ccjk_tab_slots(&c->T, t, c->d4 + c->lv_off[t], scr, c->st) != 0 || ccjk_mat5(&c->T, t, scr, c->st) != 0 ||
+                    hipStreamSynchronize(c->st) != hipSuccess ||
+                    hipMemcpy(c->h4 + c->lv_offh[t], c->d4 + c->lv_off[t], (size_t)NMAT_ST * C * sizeof(int16_t),
                               hipMemcpyDeviceToHost) != hipSuccess ||
-                    ccjk_mat5(&c->T, t, scr, c->st) != 0 || hipStreamSynchronize(c->st) != hipSuccess ||
                     hipMemcpy(c->h4 + c->lv_offh[t] + (size_t)NMAT_ST * C, scr, (size_t)NMAT_REC * C * sizeof(int16_t),
                               hipMemcpyDeviceToHost) != hipSuccess)
                     rc = set_err(c, CCJ_E_HIP, "ccj_sync_host: mirror copy of level %d failed", t);
@@ -2129,6 +2148,7 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
     hipFree(c->d_lord);
     hipFree(c->d_lord_off);
     hipFree(c->d_wbw);
+    hipFree(c->d_tab);
     hipFree(c->pmx_alloc);
     hipFree(c->d_ldx);
     hipFree(c->d_il);

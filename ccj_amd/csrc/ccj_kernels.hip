@@ -1,8 +1,10 @@
 // ccj_kernels.hip — hand-written HIP kernels (gfx950, wave64) for the CCJ MFE fill.
 //
 // Schedule: for sigma = 0..n-1
-//     k_diag2d(sigma)   : every 2-D interval value of span sigma (V, P, WBP, WPP, WMv, WMp, WM)
-//     k_level4d(t=sigma): every 4-D cell of level t = (j-i)+(l-k), all 22 gap matrices
+//     k_diag2d(sigma)   : every 2-D interval value of span sigma (V, P, WBP, WPP, WMv, WMp, WM), and
+//                         span sigma of the PL / PR multiloop tables (six gap matrices that depend
+//                         on two indices only, ccj_mloop2d.h)
+//     k_level4d(t=sigma): every 4-D cell of level t = (j-i)+(l-k), the other 16 gap matrices
 // Level t reads only 4-D levels < t and 2-D spans <= t-1; span sigma reads 4-D levels <= sigma-3.
 // Within a cell the 22 recurrences run in the reference's order (pseudo_loop.cc:85-127), so the
 // same-cell reads (PfromL/PfromR/PfromO/PK read PL/PR/PM/PO of the cell) see the finished
@@ -190,6 +192,9 @@ __global__ void k_init2d(DevTables T, int total) {
         T.WB[x] = 0;
         T.WP[x] = 0;
         T.WBW[x] = make_int2(INF + 1, 0);
+        // the PL / PR multiloop tables (ccj_mloop2d.h): never set = 32767, like a Matrix4D cell
+#pragma unroll
+        for (int f = 0; f < 6; ++f) T.tab[f * T.tabN + x] = (int16_t)INTERN_INF;
     }
 }
 
@@ -226,12 +231,50 @@ __global__ void k_precompute_ie(DevTables T) {
 // ------------------------------------------------------------------------------------------
 // Band-sharded fills partition each span: interval i belongs to rank (i-1) % G, and
 // the level-sigma exchange carries the span's values to the other ranks (k_dtail_pack / _unpack).
-__global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, int rank) {
+// The workgroups from nb on are extra work items of the launch: span sigma of the PL / PR multiloop
+// tables (ccj_mloop2d.h), one wave per interval (p, q = p+sigma), every interval whatever the shard
+// (each rank computes the whole tables from the replicated 2-D spans).  They read WBP of spans <=
+// sigma-1 and table spans < sigma, all finished by earlier launches, and nothing of this launch.
+__device__ __forceinline__ void diag2d_tables(const DevTables &T, int sigma, int item) {
+    const int n = T.n, rs = T.rs, w = sigma;
+    const int p = 1 + item, q = p + w;
+    if (q > n) return;  // whole wave
+    const int lane = threadIdx.x & 63;
+    const int cp = T.pen.cp;
+    const int16_t *F00 = T.tab, *F10 = T.tab + 2 * T.tabN, *G00 = T.tab + 3 * T.tabN;
+    Mloop2dAcc L = mloop2d_begin(T.pen.bp), R = L;
+    for (int s = 1 + lane; s <= w; s += 64) {
+#ifdef CCJ_DEBUG_BOUNDS
+        if (p + s > n || q - s + 1 < 1 || w - s < 0) atomicOr(T.err, 512);
+#endif
+        const int head = T.WBW[(s - 1) * rs + p].x, tail = T.WBW[(s - 1) * rs + q - s + 1].x;
+        const int o = (w - s) * rs + p;  // span w-s: (p, q-s) at o, (p+s, q) at o+s
+        mloop2d_step(L, true, s, w, cp, head, tail, F00[o + s], F00[o], F10[o]);
+        mloop2d_step(R, false, s, w, cp, head, tail, G00[o + s], G00[o], 0);
+    }
+    L.m00 = wave_min(L.m00); L.m01 = wave_min(L.m01); L.m10 = wave_min(L.m10);
+    R.m00 = wave_min(R.m00); R.m01 = wave_min(R.m01); R.m10 = wave_min(R.m10);
+    if (lane != 0) return;
+    if (w >= 1) {
+        const int o = (w - 1) * rs + p;  // span w-1: (k, l-1) at o, (k+1, l) at o+1
+        mloop2d_right_seed(R, w, cp, T.tab[4 * T.tabN + o], T.tab[5 * T.tabN + o + 1]);
+    }
+    const int cell = w * rs + p;
+    const int v[6] = {L.m00, L.m01, L.m10, R.m00, R.m01, R.m10};
+#pragma unroll
+    for (int f = 0; f < 6; ++f) T.tab[f * T.tabN + cell] = (int16_t)mloop2d_store(v[f]);
+}
+
+__global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, int rank, int nb) {
 #ifdef CCJ_DEBUG_BOUNDS
     g_dbg_err = T.err;
 #endif
     TL_STAMP(sigma == L_ - 1 || sigma == L_ ? 7 : -1);
     TL_META(sigma);
+    if ((int)blockIdx.x >= nb) {  // whole workgroup: no barrier below is reached
+        diag2d_tables(T, sigma, ((int)blockIdx.x - nb) * 4 + (int)(threadIdx.x >> 6));
+        return;
+    }
     __shared__ int red[4];
     __shared__ int sh_v, sh_p;
     const int n = T.n, rs = T.rs;
@@ -1131,7 +1174,10 @@ __device__ __forceinline__ int lo16(unsigned w) { return (int)(int16_t)(w & 0xff
 __device__ __forceinline__ int hi16(unsigned w) { return (int)w >> 16; }
 
 // ints per lane a leader's split wave hands to part 0: the followers' slices r = 1..R-1 of one side
-constexpr int LEAD_RED = 15 * SHARE_R;
+constexpr int LA_I = 5, LA_J = 4, LB_K = 4, LB_L = 7;  // fields per follower slice: i, j, k, l side
+constexpr int LEAD_RED = (LA_I + LA_J > LB_K + LB_L ? LA_I + LA_J : LB_K + LB_L) * SHARE_R;
+// ints per lane a split wave of the plain loops hands to part 0 (the accumulators of both loops)
+constexpr int SPLIT_RED = 16;
 
 // split-point sharing (ccj_engine.h): the SHARE_R W values of one split step, one per follower
 typedef int wv_t __attribute__((ext_vector_type(SHARE_R)));
@@ -1144,13 +1190,12 @@ __device__ __forceinline__ uint4 pack_acc(const int *f, int nf) {
 }
 
 // the three records of one cell (values as stored, i.e. already clamped)
-__device__ __forceinline__ void write_records(const DevTables &T, long long lr, int C, unsigned cell, int Lm00, int Mm00,
-                                              int Om00, int fL, int fO, int Lm10, int fMp, int K, int Rm00, int fR,
-                                              int PLR, int Mm10, int Om10) {
-    uint4 *rp = T.rec + lr;
-    rp[cell] = make_uint4(pk16(Lm00, Mm00), pk16(Om00, fL), pk16(fO, Lm10), pk16(fMp, K));
-    T.rk[(lr >> 1) + cell] = make_uint3(pk16(Rm00, Mm00), pk16(fR, PLR), pk16(K, INTERN_INF));
-    rp[(unsigned)C + cell] = make_uint4(pk16(Rm00, Mm00), pk16(Om00, Mm10), pk16(Om10, fR), pk16(fO, INTERN_INF));
+__device__ __forceinline__ void write_records(const DevTables &T, long long lr, int C, unsigned cell, int Mm00, int Om00,
+                                              int fL, int fO, int fMp, int K, int fR, int PLR, int Mm10, int Om10) {
+    rec_t *rp = T.rec + lr;
+    rp[cell] = make_uint3(pk16(Mm00, Om00), pk16(fL, fO), pk16(fMp, K));                // RA
+    T.rk[(lr >> 1) + cell] = make_uint2(pk16(Mm00, fR), pk16(PLR, K));                  // RK
+    rp[(unsigned)C + cell] = make_uint3(pk16(Mm00, Om00), pk16(Mm10, Om10), pk16(fR, fO));  // RL
 }
 
 
@@ -1227,7 +1272,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     TL_STAMP(t == L_ ? (LEAD ? 1 : 0) : -1);
     // split > 1 (late, narrow levels): the split waves of one 64-cell chunk share the a/b loops
     // (step s = part + 1, part + 1 + split, ...) and min-reduce their partial results through LDS.
-    extern __shared__ int red[];  // [chunk][part-1][22][64], split > 1 only
+    extern __shared__ int red[];  // [chunk][part-1][SPLIT_RED][64], split > 1 only
     const int n = T.n, rs = T.rs;
     const int bid = blockIdx.x;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1318,10 +1363,10 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 
     // ---- fused a-loop: split point d inside [i, j] ----
     const int seed = INTERN_INF + bp;  // A-Q3 seeds
-    int pLm00 = seed, pLm01 = INF, pLm10 = INF, pMm00 = seed, pMm10 = INF;
+    int pMm00 = seed, pMm10 = INF;
     int pOm00 = seed, pOm10 = INF;
     int fL1 = INF, fL2 = INF, fM = INF, fO1 = INF, pK1 = INF;
-    struct AV { int2 w2i, w2j; uint4 wi, wj; int s; };  // raw loads of one split step
+    struct AV { int2 w2i, w2j; rec_t wi, wj; int s; };  // raw loads of one split step
     auto load_a = [&](int s) {
         AV v;
         v.s = s;
@@ -1339,30 +1384,27 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Ui = (a - s) * L.M + s;                          // X(d,j,k,l), d = i+s: lane L0 + h*s
         const int Uj = (a - s) * L.M + s * m + ((s * (s + 1)) >> 1);  // X(i,d,k,l), d = j-s: lane L0
         const unsigned lh = L0 + uh * (unsigned)s;
-        // one RA record per side (ccj_engine.h): x = Lm00|Mm00, y = Om00|fL, z = fO|Lm10, w = fMp|K
-        const uint4 *rp = T.rec + L.lr;
+        // one RA record per side (ccj_engine.h): x = Mm00|Om00, y = fL|fO, z = fMp|K
+        const rec_t *rp = T.rec + L.lr;
         CHKR(L.lr + (unsigned)Ui + lh);
         CHKR(L.lr + (unsigned)Uj + L0);
         v.wi = rp[(unsigned)Ui + lh];
         v.wj = rp[(unsigned)Uj + L0];
         return v;
     };
+    // (the PL multiloop family's five terms, :449-486, are not here: 2-D tables, ccj_mloop2d.h)
     auto step_a = [&](const AV &v, int mask) {
         const int wbp_i = v.w2i.x, wp_i = v.w2i.y, wbp_j = v.w2j.x, wp_j = v.w2j.y;
         const int wb_i = WBD(wbp_i, v.s), wb_j = WBD(wbp_j, v.s);
-        const int Lm00i = lo16(v.wi.x), Mm00i = hi16(v.wi.x), Om00i = lo16(v.wi.y), fLi = hi16(v.wi.y), fOi = lo16(v.wi.z);
-        const int Lm00j = lo16(v.wj.x), Mm00j = hi16(v.wj.x), fLj = hi16(v.wj.y), Lm10j = hi16(v.wj.z);
-        const int fMpj = lo16(v.wj.w), Kj = hi16(v.wj.w);
-        pLm00 = imin(pLm00, imin(wb_i + Lm00i, Lm00j + wb_j));  // :449-458
-        pLm01 = imin(pLm01, Lm00j + wbp_j);                     // :468-471
-        pLm10 = imin(pLm10, wbp_i + Lm00i);                     // :481-483
+        const int Mm00i = lo16(v.wi.x), Om00i = hi16(v.wi.x), fLi = lo16(v.wi.y), fOi = hi16(v.wi.y);
+        const int Mm00j = lo16(v.wj.x), fLj = lo16(v.wj.y);
+        const int fMpj = lo16(v.wj.z), Kj = hi16(v.wj.z);
         pMm00 = imin(pMm00, Mm00j + wb_j);                      // :548-551
         pMm10 = imin(pMm10, wbp_i + Mm00i);                     // :581-584
         pOm00 = imin(pOm00, wb_i + Om00i);                      // :599-602
         pOm10 = imin(pOm10, wbp_i + Om00i);                     // :632-635
         fL1 = imin(fL1, fLi + wp_i + mask);        // PfromL(d,j,k,l) + WP(i,d-1)      :357-359
         fO1 = imin(fO1, fOi + wp_i + mask);        // PfromO(d,j,k,l) + WP(i,d-1)      :425-427
-        pLm10 = imin(pLm10, Lm10j + wb_j + mask);  // PLmloop10(i,d,k,l) + WB(d+1,j)   :484-486
         fL2 = imin(fL2, fLj + wp_j + mask);        // PfromL(i,d,k,l) + WP(d+1,j)      :360-361
         fM = imin(fM, fMpj + wp_j + mask);         // PfromMprime(i,d,k,l) + WP(d+1,j) :399-401
         pK1 = imin(pK1, Kj + wp_j + mask);         // PK(i,d,k,l) + WP(d+1,j)          :184-187
@@ -1372,12 +1414,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     //   j side: cell (i, j+r, k, l) (level t+r, block a+r, row h-r), term X(i,j-s,k,l) + W(j-s+1, j+r)
     // Both followers mask the same last split point (d = j / d = i) as the leader.
     auto lead_a = [&]() {
-        int AI_[SHARE_R][7], AJ_[SHARE_R][7];
+        int AI_[SHARE_R][LA_I], AJ_[SHARE_R][LA_J];
 #pragma unroll
-        for (int r = 0; r < SHARE_R; ++r)
+        for (int r = 0; r < SHARE_R; ++r) {
 #pragma unroll
-            for (int f = 0; f < 7; ++f) AI_[r][f] = AJ_[r][f] = INF;
-        struct LA { uint4 wi, wj; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
+            for (int f = 0; f < LA_I; ++f) AI_[r][f] = INF;
+#pragma unroll
+            for (int f = 0; f < LA_J; ++f) AJ_[r][f] = INF;
+        }
+        struct LA { rec_t wi, wj; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
         auto ld = [&](int s) {
             LA v;
             v.s = s;
@@ -1385,7 +1430,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             const int Ui = (a - s) * L.M + s;
             const int Uj = (a - s) * L.M + s * m + ((s * (s + 1)) >> 1);
             const unsigned lh = L0 + uh * (unsigned)s;
-            const uint4 *rp = T.rec + L.lr;
+            const rec_t *rp = T.rec + L.lr;
             CHKR(L.lr + (unsigned)Ui + lh);
             CHKR(L.lr + (unsigned)Uj + L0);
             v.wi = rp[(unsigned)Ui + lh];
@@ -1406,29 +1451,23 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             return v;
         };
         auto st = [&](const LA &v, int mask) {
-            const int Lm00i = lo16(v.wi.x), Mm00i = hi16(v.wi.x), Om00i = lo16(v.wi.y), fLi = hi16(v.wi.y);
-            const int fOi = lo16(v.wi.z);
-            const int Lm00j = lo16(v.wj.x), Mm00j = hi16(v.wj.x), fLj = hi16(v.wj.y), Lm10j = hi16(v.wj.z);
-            const int fMpj = lo16(v.wj.w), Kj = hi16(v.wj.w);
+            const int Mm00i = lo16(v.wi.x), Om00i = hi16(v.wi.x), fLi = lo16(v.wi.y), fOi = hi16(v.wi.y);
+            const int Mm00j = lo16(v.wj.x), fLj = lo16(v.wj.y);
+            const int fMpj = lo16(v.wj.z), Kj = hi16(v.wj.z);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
                 const int wbpi = v.q[r].x, wpi = v.q[r].y, wbi = WBD(wbpi, v.s + r);
-                const int wbpj = v.p[r].x, wpj = v.p[r].y, wbj = WBD(wbpj, v.s + r);
+                const int wpj = v.p[r].y, wbj = WBD(v.p[r].x, v.s + r);
                 int *I = AI_[r], *J = AJ_[r];
-                I[0] = imin(I[0], wbi + Lm00i);          // PLmloop00 :449-458
-                I[1] = imin(I[1], wbpi + Lm00i);         // PLmloop10 :481-483
-                I[2] = imin(I[2], wbpi + Mm00i);         // PMmloop10 :581-584
-                I[3] = imin(I[3], wbi + Om00i);          // POmloop00 :599-602
-                I[4] = imin(I[4], wbpi + Om00i);         // POmloop10 :632-635
-                I[5] = imin(I[5], fLi + wpi + mask);     // PfromL    :357-359
-                I[6] = imin(I[6], fOi + wpi + mask);     // PfromO    :425-427
-                J[0] = imin(J[0], Lm00j + wbj);          // PLmloop00
-                J[1] = imin(J[1], Lm00j + wbpj);         // PLmloop01 :468-471
-                J[2] = imin(J[2], Mm00j + wbj);          // PMmloop00 :548-551
-                J[3] = imin(J[3], Lm10j + wbj + mask);   // PLmloop10 :484-486
-                J[4] = imin(J[4], fLj + wpj + mask);     // PfromL    :360-361
-                J[5] = imin(J[5], fMpj + wpj + mask);    // PfromM    :399-401
-                J[6] = imin(J[6], Kj + wpj + mask);      // PK        :184-187
+                I[0] = imin(I[0], wbpi + Mm00i);         // PMmloop10 :581-584
+                I[1] = imin(I[1], wbi + Om00i);          // POmloop00 :599-602
+                I[2] = imin(I[2], wbpi + Om00i);         // POmloop10 :632-635
+                I[3] = imin(I[3], fLi + wpi + mask);     // PfromL    :357-359
+                I[4] = imin(I[4], fOi + wpi + mask);     // PfromO    :425-427
+                J[0] = imin(J[0], Mm00j + wbj);          // PMmloop00 :548-551
+                J[1] = imin(J[1], fLj + wpj + mask);     // PfromL    :360-361
+                J[2] = imin(J[2], fMpj + wpj + mask);    // PfromM    :399-401
+                J[3] = imin(J[3], Kj + wpj + mask);      // PK        :184-187
             }
         };
         if (1 + part <= a) pipe_scan_lead<LA>(1 + part, split, a, a, ld, st);
@@ -1439,40 +1478,39 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             int *slot = red + (wib / split) * (split - 1) * LEAD_RED * 64 + lane;
             if (part > 0) {
 #pragma unroll
-                for (int r = 0; r < SHARE_R; ++r)
+                for (int r = 0; r < SHARE_R; ++r) {
+                    if (r < r0) continue;
 #pragma unroll
-                    for (int f = 0; f < 7; ++f) {
-                        if (r < r0) continue;
-                        slot[((part - 1) * LEAD_RED + r * 14 + f) * 64] = AI_[r][f];
-                        slot[((part - 1) * LEAD_RED + r * 14 + 7 + f) * 64] = AJ_[r][f];
-                    }
+                    for (int f = 0; f < LA_I; ++f) slot[((part - 1) * LEAD_RED + r * (LA_I + LA_J) + f) * 64] = AI_[r][f];
+#pragma unroll
+                    for (int f = 0; f < LA_J; ++f) slot[((part - 1) * LEAD_RED + r * (LA_I + LA_J) + LA_I + f) * 64] = AJ_[r][f];
+                }
             }
             __syncthreads();
             if (part == 0)
                 for (int p = 1; p < split; ++p)
 #pragma unroll
-                    for (int r = 0; r < SHARE_R; ++r)
+                    for (int r = 0; r < SHARE_R; ++r) {
+                        if (r < r0) continue;
 #pragma unroll
-                        for (int f = 0; f < 7; ++f) {
-                            if (r < r0) continue;
-                            AI_[r][f] = imin(AI_[r][f], slot[((p - 1) * LEAD_RED + r * 14 + f) * 64]);
-                            AJ_[r][f] = imin(AJ_[r][f], slot[((p - 1) * LEAD_RED + r * 14 + 7 + f) * 64]);
-                        }
+                        for (int f = 0; f < LA_I; ++f)
+                            AI_[r][f] = imin(AI_[r][f], slot[((p - 1) * LEAD_RED + r * (LA_I + LA_J) + f) * 64]);
+#pragma unroll
+                        for (int f = 0; f < LA_J; ++f)
+                            AJ_[r][f] = imin(AJ_[r][f], slot[((p - 1) * LEAD_RED + r * (LA_I + LA_J) + LA_I + f) * 64]);
+                    }
             __syncthreads();
         }
         {
-        pLm00 = imin(pLm00, imin(AI_[0][0], AJ_[0][0]));
-        pLm10 = imin(AI_[0][1], AJ_[0][3]);
-        pMm10 = AI_[0][2];
-        pOm00 = imin(pOm00, AI_[0][3]);
-        pOm10 = AI_[0][4];
-        fL1 = AI_[0][5];
-        fO1 = AI_[0][6];
-        pLm01 = AJ_[0][1];
-        pMm00 = imin(pMm00, AJ_[0][2]);
-        fL2 = AJ_[0][4];
-        fM = AJ_[0][5];
-        pK1 = AJ_[0][6];
+        pMm10 = AI_[0][0];
+        pOm00 = imin(pOm00, AI_[0][1]);
+        pOm10 = AI_[0][2];
+        fL1 = AI_[0][3];
+        fO1 = AI_[0][4];
+        pMm00 = imin(pMm00, AJ_[0][0]);
+        fL2 = AJ_[0][1];
+        fM = AJ_[0][2];
+        pK1 = AJ_[0][3];
         }
         if (!lane_ok || part != 0) return;
 #ifdef CCJ_ABLATE_NOACC  // timing only: no partial-record stores (followers read stale partials)
@@ -1488,13 +1526,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             if (i - r >= 1) {
                 const unsigned idx = (unsigned)((a + r) * Mf) + L0 - (unsigned)(r * (h + 1));
                 CHKA(idx);
-                ring[(long long)AI * T.accC + idx] = pack_acc(AI_[r], 7);
+                const uint4 v = pack_acc(AI_[r], LA_I);
+                *(uint3 *)(ring + (long long)AI * T.accC + idx) = make_uint3(v.x, v.y, v.z);
             }
             if (h - r >= 0) {
                 const int hh = h - r;
                 const unsigned idx = (unsigned)((a + r) * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                ring[(long long)AJ * T.accC + idx] = pack_acc(AJ_[r], 7);
+                const uint4 v = pack_acc(AJ_[r], LA_J);
+                *(uint2 *)(ring + (long long)AJ * T.accC + idx) = make_uint2(v.x, v.y);
             }
         }
     };
@@ -1511,24 +1551,22 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const uint4 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
         const unsigned idx = (unsigned)(a * Mt) + L0;
         CHKA(idx);
-        const uint4 pi = ring[(long long)AI * T.accC + idx], pj = ring[(long long)AJ * T.accC + idx];
-        pLm00 = imin(pLm00, imin(lo16(pi.x), lo16(pj.x)));
-        pLm10 = imin(pLm10, imin(hi16(pi.x), hi16(pj.y)));
-        pMm10 = imin(pMm10, lo16(pi.y));
-        pOm00 = imin(pOm00, hi16(pi.y));
-        pOm10 = imin(pOm10, lo16(pi.z));
-        fL1 = imin(fL1, hi16(pi.z));
-        fO1 = imin(fO1, lo16(pi.w));
-        pLm01 = imin(pLm01, hi16(pj.x));
-        pMm00 = imin(pMm00, lo16(pj.y));
-        fL2 = imin(fL2, lo16(pj.z));
-        fM = imin(fM, hi16(pj.z));
-        pK1 = imin(pK1, lo16(pj.w));
+        const uint3 pi = *(const uint3 *)(ring + (long long)AI * T.accC + idx);
+        const uint2 pj = *(const uint2 *)(ring + (long long)AJ * T.accC + idx);
+        pMm10 = imin(pMm10, lo16(pi.x));
+        pOm00 = imin(pOm00, hi16(pi.x));
+        pOm10 = imin(pOm10, lo16(pi.y));
+        fL1 = imin(fL1, hi16(pi.y));
+        fO1 = imin(fO1, lo16(pi.z));
+        pMm00 = imin(pMm00, lo16(pj.x));
+        fL2 = imin(fL2, hi16(pj.x));
+        fM = imin(fM, lo16(pj.y));
+        pK1 = imin(pK1, hi16(pj.y));
     }
     // ---- fused b-loop: split point d inside [k, l] ----
-    int pRm00 = seed, pRm01 = INF, pRm10 = INF, pMm01 = INF, pOm01 = INF;
+    int pMm01 = INF, pOm01 = INF;
     int fR1 = INF, fR2 = INF, fMp = INF, fO2 = INF, pK2 = INF;
-    struct BV { int2 w2k, w2l; uint3 wk; uint4 wl; int s; };  // raw loads of one split step
+    struct BV { int2 w2k, w2l; rk_t wk; rec_t wl; int s; };  // raw loads of one split step
     auto load_b = [&](int s) {
         BV v;
         v.s = s;
@@ -1546,25 +1584,23 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Uk = a * L.M + s * m + ((s * (s + 1)) >> 1);  // X(i,j,d,l), d = k+s: lane L0
         const int Ul = a * L.M;                                 // X(i,j,k,d), d = l-s: lane L0 + h*s
         const unsigned lh = L0 + uh * (unsigned)s;
-        // RK at X(i,j,d,l): x = Rm00|Mm00, y = fR|min(PL,PR), z = K|-
-        // RL at X(i,j,k,d): x = Rm00|Mm00, y = Om00|Mm10, z = Om10|fR, w = fO|-
-        const uint4 *rp = T.rec + L.lr;
-        const uint3 *kp = T.rk + (L.lr >> 1);
+        // RK at X(i,j,d,l): x = Mm00|fR, y = min(PL,PR)|K
+        // RL at X(i,j,k,d): x = Mm00|Om00, y = Mm10|Om10, z = fR|fO
+        const rec_t *rp = T.rec + L.lr;
+        const rk_t *kp = T.rk + (L.lr >> 1);
         CHKK((L.lr >> 1) + (unsigned)Uk + L0);
         CHKR(L.lr + L.C + (unsigned)Ul + lh);
         v.wk = kp[(unsigned)Uk + L0];
         v.wl = rp[(unsigned)(L.C + Ul) + lh];
         return v;
     };
+    // (the PR multiloop family's four terms, :499-537, are not here: 2-D tables, ccj_mloop2d.h)
     auto step_b = [&](const BV &v, int mask) {
-        const int wbp_k = v.w2k.x, wp_k = v.w2k.y, wbp_l = v.w2l.x, wp_l = v.w2l.y;
-        const int wb_k = WBD(wbp_k, v.s), wb_l = WBD(wbp_l, v.s);
-        const int Rm00k = lo16(v.wk.x), Mm00k = hi16(v.wk.x), fRk = lo16(v.wk.y), PLRk = hi16(v.wk.y), Kk = lo16(v.wk.z);
-        const int Rm00l = lo16(v.wl.x), Mm00l = hi16(v.wl.x), Om00l = lo16(v.wl.y), Mm10l = hi16(v.wl.y);
-        const int Om10l = lo16(v.wl.z), fRl = hi16(v.wl.z), fOl = lo16(v.wl.w);
-        pRm00 = imin(pRm00, imin(wb_k + Rm00k, Rm00l + wb_l));  // :499-508
-        pRm10 = imin(pRm10, wbp_k + Rm00k);                     // :534-537
-        pRm01 = imin(pRm01, Rm00l + wbp_l);                     // :520-523
+        const int wp_k = v.w2k.y, wbp_l = v.w2l.x, wp_l = v.w2l.y;
+        const int wb_k = WBD(v.w2k.x, v.s), wb_l = WBD(wbp_l, v.s);
+        const int Mm00k = lo16(v.wk.x), fRk = hi16(v.wk.x), PLRk = lo16(v.wk.y), Kk = hi16(v.wk.y);
+        const int Mm00l = lo16(v.wl.x), Om00l = hi16(v.wl.x), Mm10l = lo16(v.wl.y), Om10l = hi16(v.wl.y);
+        const int fRl = lo16(v.wl.z), fOl = hi16(v.wl.z);
         pMm00 = imin(pMm00, Mm00k + wb_k);                      // :552-555
         pMm01 = imin(pMm01, Mm00l + wbp_l);                     // :567-570
         pOm00 = imin(pOm00, Om00l + wb_l);                      // :603-606
@@ -1581,15 +1617,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     //   k side: cell (i, j, k-r, l) (level t+r, block a, row h-r), term X(i,j,k+s,l) + W(k-r, k+s-1)
     //   l side: cell (i, j, k, l+r) (level t+r, block a, row h),   term X(i,j,k,l-s) + W(l-s+1, l+r)
     auto lead_b = [&]() {
-        int AK_[SHARE_R][6], AL_[SHARE_R][9];
+        int AK_[SHARE_R][LB_K], AL_[SHARE_R][LB_L];
 #pragma unroll
         for (int r = 0; r < SHARE_R; ++r) {
 #pragma unroll
-            for (int f = 0; f < 6; ++f) AK_[r][f] = INF;
+            for (int f = 0; f < LB_K; ++f) AK_[r][f] = INF;
 #pragma unroll
-            for (int f = 0; f < 9; ++f) AL_[r][f] = INF;
+            for (int f = 0; f < LB_L; ++f) AL_[r][f] = INF;
         }
-        struct LB { uint3 wk; uint4 wl; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
+        struct LB { rk_t wk; rec_t wl; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
         auto ld = [&](int s) {
             LB v;
             v.s = s;
@@ -1597,8 +1633,8 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             const int Uk = a * L.M + s * m + ((s * (s + 1)) >> 1);
             const int Ul = a * L.M;
             const unsigned lh = L0 + uh * (unsigned)s;
-            const uint4 *rp = T.rec + L.lr;
-            const uint3 *kp = T.rk + (L.lr >> 1);
+            const rec_t *rp = T.rec + L.lr;
+            const rk_t *kp = T.rk + (L.lr >> 1);
             CHKK((L.lr >> 1) + (unsigned)Uk + L0);
             CHKR(L.lr + L.C + (unsigned)Ul + lh);
             v.wk = kp[(unsigned)Uk + L0];
@@ -1617,30 +1653,25 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             return v;
         };
         auto st = [&](const LB &v, int mask) {
-            const int Rm00k = lo16(v.wk.x), Mm00k = hi16(v.wk.x), fRk = lo16(v.wk.y), PLRk = hi16(v.wk.y);
-            const int Kk = lo16(v.wk.z);
-            const int Rm00l = lo16(v.wl.x), Mm00l = hi16(v.wl.x), Om00l = lo16(v.wl.y), Mm10l = hi16(v.wl.y);
-            const int Om10l = lo16(v.wl.z), fRl = hi16(v.wl.z), fOl = lo16(v.wl.w);
+            const int Mm00k = lo16(v.wk.x), fRk = hi16(v.wk.x), PLRk = lo16(v.wk.y), Kk = hi16(v.wk.y);
+            const int Mm00l = lo16(v.wl.x), Om00l = hi16(v.wl.x), Mm10l = lo16(v.wl.y), Om10l = hi16(v.wl.y);
+            const int fRl = lo16(v.wl.z), fOl = hi16(v.wl.z);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
-                const int wbpk = v.q[r].x, wpk = v.q[r].y, wbk = WBD(wbpk, v.s + r);
+                const int wpk = v.q[r].y, wbk = WBD(v.q[r].x, v.s + r);
                 const int wbpl = v.p[r].x, wpl_ = v.p[r].y, wbl = WBD(wbpl, v.s + r);
                 int *K = AK_[r], *Q = AL_[r];
-                K[0] = imin(K[0], wbk + Rm00k);             // PRmloop00 :499-508
-                K[1] = imin(K[1], wbpk + Rm00k);            // PRmloop10 :534-537
-                K[2] = imin(K[2], Mm00k + wbk);             // PMmloop00 :552-555
-                K[3] = imin(K[3], fRk + wpk + mask);        // PfromR    :379-381
-                K[4] = imin(K[4], PLRk + PB + wpk + mask);  // PfromMprime :412-414
-                K[5] = imin(K[5], Kk + wpk + mask);         // PK        :189-192
-                Q[0] = imin(Q[0], Rm00l + wbl);             // PRmloop00
-                Q[1] = imin(Q[1], Rm00l + wbpl);            // PRmloop01 :520-523
-                Q[2] = imin(Q[2], Mm00l + wbpl);            // PMmloop01 :567-570
-                Q[3] = imin(Q[3], Om00l + wbl);             // POmloop00 :603-606
-                Q[4] = imin(Q[4], Om00l + wbpl);            // POmloop01 :618-621
-                Q[5] = imin(Q[5], Mm10l + wbl + mask);      // PMmloop10 :585-588
-                Q[6] = imin(Q[6], Om10l + wbl + mask);      // POmloop10 :636-639
-                Q[7] = imin(Q[7], fRl + wpl_ + mask);       // PfromR    :382-383
-                Q[8] = imin(Q[8], fOl + wpl_ + mask);       // PfromO    :429-431
+                K[0] = imin(K[0], Mm00k + wbk);             // PMmloop00 :552-555
+                K[1] = imin(K[1], fRk + wpk + mask);        // PfromR    :379-381
+                K[2] = imin(K[2], PLRk + PB + wpk + mask);  // PfromMprime :412-414
+                K[3] = imin(K[3], Kk + wpk + mask);         // PK        :189-192
+                Q[0] = imin(Q[0], Mm00l + wbpl);            // PMmloop01 :567-570
+                Q[1] = imin(Q[1], Om00l + wbl);             // POmloop00 :603-606
+                Q[2] = imin(Q[2], Om00l + wbpl);            // POmloop01 :618-621
+                Q[3] = imin(Q[3], Mm10l + wbl + mask);      // PMmloop10 :585-588
+                Q[4] = imin(Q[4], Om10l + wbl + mask);      // POmloop10 :636-639
+                Q[5] = imin(Q[5], fRl + wpl_ + mask);       // PfromR    :382-383
+                Q[6] = imin(Q[6], fOl + wpl_ + mask);       // PfromO    :429-431
             }
         };
         if (1 + part <= b) pipe_scan_lead<LB>(1 + part, split, b, b, ld, st);
@@ -1652,9 +1683,9 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                 for (int r = 0; r < SHARE_R; ++r) {
                     if (r < r0) continue;
 #pragma unroll
-                    for (int f = 0; f < 6; ++f) slot[((part - 1) * LEAD_RED + r * 15 + f) * 64] = AK_[r][f];
+                    for (int f = 0; f < LB_K; ++f) slot[((part - 1) * LEAD_RED + r * (LB_K + LB_L) + f) * 64] = AK_[r][f];
 #pragma unroll
-                    for (int f = 0; f < 9; ++f) slot[((part - 1) * LEAD_RED + r * 15 + 6 + f) * 64] = AL_[r][f];
+                    for (int f = 0; f < LB_L; ++f) slot[((part - 1) * LEAD_RED + r * (LB_K + LB_L) + LB_K + f) * 64] = AL_[r][f];
                 }
             }
             __syncthreads();
@@ -1664,29 +1695,26 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                     for (int r = 0; r < SHARE_R; ++r) {
                         if (r < r0) continue;
 #pragma unroll
-                        for (int f = 0; f < 6; ++f)
-                            AK_[r][f] = imin(AK_[r][f], slot[((p - 1) * LEAD_RED + r * 15 + f) * 64]);
+                        for (int f = 0; f < LB_K; ++f)
+                            AK_[r][f] = imin(AK_[r][f], slot[((p - 1) * LEAD_RED + r * (LB_K + LB_L) + f) * 64]);
 #pragma unroll
-                        for (int f = 0; f < 9; ++f)
-                            AL_[r][f] = imin(AL_[r][f], slot[((p - 1) * LEAD_RED + r * 15 + 6 + f) * 64]);
+                        for (int f = 0; f < LB_L; ++f)
+                            AL_[r][f] = imin(AL_[r][f], slot[((p - 1) * LEAD_RED + r * (LB_K + LB_L) + LB_K + f) * 64]);
                     }
             __syncthreads();
         }
         {
-        pRm00 = imin(pRm00, imin(AK_[0][0], AL_[0][0]));
-        pRm10 = AK_[0][1];
-        pMm00 = imin(pMm00, AK_[0][2]);
-        fR1 = AK_[0][3];
-        fMp = AK_[0][4];
-        pK2 = AK_[0][5];
-        pRm01 = AL_[0][1];
-        pMm01 = AL_[0][2];
-        pOm00 = imin(pOm00, AL_[0][3]);
-        pOm01 = AL_[0][4];
-        pMm10 = imin(pMm10, AL_[0][5]);
-        pOm10 = imin(pOm10, AL_[0][6]);
-        fR2 = AL_[0][7];
-        fO2 = AL_[0][8];
+        pMm00 = imin(pMm00, AK_[0][0]);
+        fR1 = AK_[0][1];
+        fMp = AK_[0][2];
+        pK2 = AK_[0][3];
+        pMm01 = AL_[0][0];
+        pOm00 = imin(pOm00, AL_[0][1]);
+        pOm01 = AL_[0][2];
+        pMm10 = imin(pMm10, AL_[0][3]);
+        pOm10 = imin(pOm10, AL_[0][4]);
+        fR2 = AL_[0][5];
+        fO2 = AL_[0][6];
         }
         if (!lane_ok || part != 0) return;
 #ifdef CCJ_ABLATE_NOACC
@@ -1699,20 +1727,17 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             if (tf >= T.g_hi) break;
             const int Mf = LD[tf].M, mf = m - r;
             uint4 *ring = T.acc + (long long)((tf % SHARE_SLOTS) * SHARE_NACC) * T.accC;
-            if (h - r >= 0) {  // k side: AK slots 0..5 (12 bytes; slot 6 belongs to the l-side leader)
+            if (h - r >= 0) {  // k side
                 const int hh = h - r;
                 const unsigned idx = (unsigned)(a * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                const uint4 v = pack_acc(AK_[r], 6);
-                *(uint3 *)(ring + (long long)AK * T.accC + idx) = make_uint3(v.x, v.y, v.z);
+                const uint4 v = pack_acc(AK_[r], LB_K);
+                *(uint2 *)(ring + (long long)AK * T.accC + idx) = make_uint2(v.x, v.y);
             }
-            if (i <= m - h - r) {  // l side: AL, and its 9th field into AK slot 6 of the same cell
+            if (i <= m - h - r) {  // l side
                 const unsigned idx = (unsigned)(a * Mf) + L0 - (unsigned)(h * r);
                 CHKA(idx);
-                ring[(long long)AL * T.accC + idx] = pack_acc(AL_[r], 8);
-                // bytes 12..15 of AK (slot 6 and the unused slot 7): with the k side's 12 bytes the
-                // whole 16-byte record is written (measured equal to a 2-byte store of slot 6)
-                ((unsigned *)(ring + (long long)AK * T.accC + idx))[3] = pk16(clamp_store(AL_[r][8]), INTERN_INF);
+                ring[(long long)AL * T.accC + idx] = pack_acc(AL_[r], LB_L);
             }
         }
     };
@@ -1728,70 +1753,64 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const uint4 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
         const unsigned idx = (unsigned)(a * Mt) + L0;
         CHKA(idx);
-        const uint4 pk = ring[(long long)AK * T.accC + idx], pl = ring[(long long)AL * T.accC + idx];
-        pRm00 = imin(pRm00, imin(lo16(pk.x), lo16(pl.x)));
-        pRm10 = imin(pRm10, hi16(pk.x));
-        pMm00 = imin(pMm00, lo16(pk.y));
-        fR1 = imin(fR1, hi16(pk.y));
-        fMp = imin(fMp, lo16(pk.z));
-        pK2 = imin(pK2, hi16(pk.z));
-        fO2 = imin(fO2, lo16(pk.w));
-        pRm01 = imin(pRm01, hi16(pl.x));
-        pMm01 = imin(pMm01, lo16(pl.y));
-        pOm00 = imin(pOm00, hi16(pl.y));
-        pOm01 = imin(pOm01, lo16(pl.z));
-        pMm10 = imin(pMm10, hi16(pl.z));
-        pOm10 = imin(pOm10, lo16(pl.w));
-        fR2 = imin(fR2, hi16(pl.w));
+        const uint2 pk = *(const uint2 *)(ring + (long long)AK * T.accC + idx);
+        const uint4 pl = ring[(long long)AL * T.accC + idx];
+        pMm00 = imin(pMm00, lo16(pk.x));
+        fR1 = imin(fR1, hi16(pk.x));
+        fMp = imin(fMp, lo16(pk.y));
+        pK2 = imin(pK2, hi16(pk.y));
+        pMm01 = imin(pMm01, lo16(pl.x));
+        pOm00 = imin(pOm00, hi16(pl.x));
+        pOm01 = imin(pOm01, lo16(pl.y));
+        pMm10 = imin(pMm10, hi16(pl.y));
+        pOm10 = imin(pOm10, lo16(pl.z));
+        fR2 = imin(fR2, hi16(pl.z));
+        fO2 = imin(fO2, lo16(pl.w));
     }
     if (split > 1) {
         // min-reduce the split waves' partial a/b-loop results; part 0 finishes the cell
-        int acc[22] = {pLm00, pLm01, pLm10, pMm00, pMm10, pOm00, pOm10, fL1, fL2, fM, fO1, pK1,
-                       pRm00, pRm01, pRm10, pMm01, pOm01, fR1, fR2, fMp, fO2, pK2};
+        int acc[SPLIT_RED] = {pMm00, pMm10, pOm00, pOm10, fL1, fL2, fM, fO1, pK1, pMm01, pOm01, fR1, fR2, fMp, fO2, pK2};
         const int cl = wib / split;
-        int *slot = red + ((cl * (split - 1) + (part - 1)) * 22) * 64 + lane;
+        int *slot = red + ((cl * (split - 1) + (part - 1)) * SPLIT_RED) * 64 + lane;
         if (part > 0)
 #pragma unroll
-            for (int x = 0; x < 22; ++x) slot[x * 64] = acc[x];
+            for (int x = 0; x < SPLIT_RED; ++x) slot[x * 64] = acc[x];
         __syncthreads();
         if (part > 0) return;
         for (int p = 1; p < split; ++p) {
-            const int *src = red + ((cl * (split - 1) + (p - 1)) * 22) * 64 + lane;
+            const int *src = red + ((cl * (split - 1) + (p - 1)) * SPLIT_RED) * 64 + lane;
 #pragma unroll
-            for (int x = 0; x < 22; ++x) acc[x] = imin(acc[x], src[x * 64]);
+            for (int x = 0; x < SPLIT_RED; ++x) acc[x] = imin(acc[x], src[x * 64]);
         }
-        pLm00 = acc[0]; pLm01 = acc[1]; pLm10 = acc[2]; pMm00 = acc[3]; pMm10 = acc[4]; pOm00 = acc[5];
-        pOm10 = acc[6]; fL1 = acc[7]; fL2 = acc[8]; fM = acc[9]; fO1 = acc[10]; pK1 = acc[11];
-        pRm00 = acc[12]; pRm01 = acc[13]; pRm10 = acc[14]; pMm01 = acc[15]; pOm01 = acc[16]; fR1 = acc[17];
-        fR2 = acc[18]; fMp = acc[19]; fO2 = acc[20]; pK2 = acc[21];
+        pMm00 = acc[0]; pMm10 = acc[1]; pOm00 = acc[2]; pOm10 = acc[3]; fL1 = acc[4]; fL2 = acc[5];
+        fM = acc[6]; fO1 = acc[7]; pK1 = acc[8]; pMm01 = acc[9]; pOm01 = acc[10]; fR1 = acc[11];
+        fR2 = acc[12]; fMp = acc[13]; fO2 = acc[14]; pK2 = acc[15];
         if (!lane_ok) return;
     }
-    // ---- single-step seeds (:519, :533, :566, :580), level t-1
-    int vPRm01 = pRm01, vPRm10 = pRm10, vPMm01 = pMm01, vPMm10 = pMm10;
+    // ---- single-step seeds (:566, :580), level t-1 (PRmloop01 / 10's, :519 / :533, are in the tables)
+    int vPMm01 = pMm01, vPMm10 = pMm10;
     {
-        const int16_t *dummy = D4;
-        (void)dummy;
         if (t >= 1) {
             const LvlDev L = LD[t - 1];
             const int16_t *lp = D4 + L.lb;
-            if (b >= 1) {
-                vPRm01 = imin(vPRm01, LDX(lp, L, PRmloop01, a * L.M, L0 + uh) + cp);          // (i,j,k,l-1)
-                vPRm10 = imin(vPRm10, LDX(lp, L, PRmloop10, a * L.M + m + 1, L0) + cp);       // (i,j,k+1,l)
-                vPMm01 = imin(vPMm01, LDX(lp, L, PMmloop01, a * L.M + m + 1, L0) + cp);       // (i,j,k+1,l)
-            }
+            if (b >= 1) vPMm01 = imin(vPMm01, LDX(lp, L, PMmloop01, a * L.M + m + 1, L0) + cp);       // (i,j,k+1,l)
             // PMmloop10 from the RL record (d4 does not store it: ccj_engine.h rec_only)
-            if (a >= 1) vPMm10 = imin(vPMm10, hi16(T.rec[L.lr + (unsigned)(L.C + (a - 1) * L.M + m + 1) + L0].y) + cp);  // (i,j-1,k,l)
+            if (a >= 1) vPMm10 = imin(vPMm10, lo16(T.rec[L.lr + (unsigned)(L.C + (a - 1) * L.M + m + 1) + L0].y) + cp);  // (i,j-1,k,l)
         }
     }
-    const int vPLm00 = pLm00, vPLm01 = pLm01, vPLm10 = pLm10, vPRm00 = pRm00, vPMm00 = pMm00;
+    const int vPMm00 = pMm00;
     const int vPOm00 = pOm00, vPOm01 = pOm01, vPOm10 = pOm10;
+    // the PL / PR multiloop tables (ccj_mloop2d.h), span-major: consecutive lanes (i) read consecutive
+    // words.  get_PLmloop / get_PRmloop read spans a-2 / b-2 <= t-2 (written by k_diag2d(<= t-2))
+    const int16_t *__restrict__ TAB = T.tab;
+    const long long tabN = T.tabN;
 
     // ---- level t-2 neighbours of PL/PR/PM/PO (stack terms, get_P?mloop, PfromX)
     const LvlDev L2 = LD[t >= 2 ? t - 2 : 0];
     const int16_t *lp2 = D4 + L2.lb;
-    // the record-carried matrices of those neighbours (PLmloop10, PfromL, PfromR, PMmloop10,
-    // POmloop10, PfromO; ccj_engine.h rec_only) from their loop records: one 16-byte load per cell
-    const uint4 *rp2 = T.rec + L2.lr;
+    // the record-carried matrices of those neighbours (PfromL, PfromR, PMmloop10, POmloop10, PfromO;
+    // ccj_engine.h rec_only) from their loop records: one 12-byte load per cell
+    const rec_t *rp2 = T.rec + L2.lr;
     // own slots of level t: k_iloop(t) left the interior-loop minima of PL/PR/PM there
     const LvlDev Lt = LD[t];
     const int C = Lt.C;
@@ -1811,9 +1830,10 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             b1 = imin(b1, imin(pin + W2E(T.ie, i, j), (int)dst[mslot(PL) * C]));
 #endif
         }
-        const uint4 ra = (a >= 2) ? rp2[(unsigned)Uin + L0 + uh] : make_uint4(0, 0, 0, 0);  // RA: ., .|fL, .|Lm10, .
-        const int b2 = (a >= 2) ? imin(hi16(ra.z), LDX(lp2, L2, PLmloop01, Uin, L0 + uh)) + apbp2 : INF;
-        const int b3 = (a >= TURN + 1) ? hi16(ra.y) : INF;
+        // get_PLmloop (:705-715): PLmloop10 / PLmloop01 of (i+1, j-1), table span a-2
+        const int ot = (a - 2) * rs + i + 1;
+        const int b2 = (a >= 2) ? imin((int)TAB[2 * tabN + ot], (int)TAB[1 * tabN + ot]) + apbp2 : INF;
+        const int b3 = (a >= TURN + 1) ? lo16(rp2[(unsigned)Uin + L0 + uh].y) : INF;  // RA: ., fL|., .
         vPL = imin(imin(b1, b2), b3);
     }
     // ---- PR (:255-275) with get_PRiloop (:717-738, k_iloop), get_PRmloop (:740-750)
@@ -1829,8 +1849,10 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             b1 = imin(b1, imin(pin + W2E(T.ie, k, l), (int)dst[mslot(PR) * C]));
 #endif
         }
-        const int b2 = (b >= 2) ? imin(LDX(lp2, L2, PRmloop10, Uin, L0 + uh), LDX(lp2, L2, PRmloop01, Uin, L0 + uh)) + apbp2 : INF;
-        const int b3 = (b >= TURN + 1) ? lo16(T.rk[(L2.lr >> 1) + (unsigned)Uin + L0 + uh].y) : INF;  // RK: ., fR|.
+        // get_PRmloop (:740-750): PRmloop10 / PRmloop01 of (k+1, l-1), table span b-2
+        const int ot = (b - 2) * rs + k + 1;
+        const int b2 = (b >= 2) ? imin((int)TAB[5 * tabN + ot], (int)TAB[4 * tabN + ot]) + apbp2 : INF;
+        const int b3 = (b >= TURN + 1) ? hi16(T.rk[(L2.lr >> 1) + (unsigned)Uin + L0 + uh].x) : INF;  // RK: .|fR, .
         vPR = imin(imin(b1, b2), b3);
     }
     // ---- PM (:277-300) with get_PMiloop (:752-773, k_iloop), get_PMmloop (:775-785)
@@ -1847,7 +1869,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             if (a >= 2 && b >= 2) b1 = imin(b1, imin(pin + W2E(T.ie, j - 1, k + 1), (int)dst[mslot(PM) * C]));
 #endif
         }
-        const int b2 = inner ? imin(hi16(rp2[(unsigned)(L2.C + Uin) + L0].y), LDX(lp2, L2, PMmloop01, Uin, L0)) + apbp2 : INF;  // RL: ., .|Mm10
+        const int b2 = inner ? imin(lo16(rp2[(unsigned)(L2.C + Uin) + L0].y), LDX(lp2, L2, PMmloop01, Uin, L0)) + apbp2 : INF;  // RL: ., Mm10|., .
         const int b3 = inner ? LDX(lp2, L2, PfromM, Uin, L0) : INF;
         const int b4 = (a == 0 && b == 0) ? 0 : INF;
         vPM = imin(imin(b1, b2), imin(b3, b4));
@@ -1859,9 +1881,9 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Uin = (a - 1) * L2.M + 1;  // (i+1, j, k, l-1): lane L0 + 2h
         int b1 = INF;
         if (l - i > TURN && inner) b1 = LDX(lp2, L2, PO, Uin, L0 + 2 * uh) + W2E(T.est, i, l);
-        const uint4 rl = inner ? rp2[(unsigned)(L2.C + Uin) + L0 + 2 * uh] : make_uint4(0, 0, 0, 0);  // RL: ., ., Om10|., fO|.
-        const int b2 = inner ? imin(lo16(rl.z), LDX(lp2, L2, POmloop01, Uin, L0 + 2 * uh)) + apbp2 : INF;
-        const int b3 = (inner && l - i >= TURN + 1) ? lo16(rl.w) : INF;
+        const rec_t rl = inner ? rp2[(unsigned)(L2.C + Uin) + L0 + 2 * uh] : make_uint3(0, 0, 0);  // RL: ., .|Om10, .|fO
+        const int b2 = inner ? imin(hi16(rl.y), LDX(lp2, L2, POmloop01, Uin, L0 + 2 * uh)) + apbp2 : INF;
+        const int b3 = (inner && l - i >= TURN + 1) ? hi16(rl.z) : INF;
         vPO = imin(imin(b1, b2), b3);
     }
 #undef LDX
@@ -1892,12 +1914,8 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     dst[mslot(PfromM) * C] = (int16_t)clamp_store(vPfromM);
     if (T.mat5) dst[mslot(PfromMprime) * C] = (int16_t)clamp_store(vPfromMp);  // record-carried (ccj_engine.h rec_only)
     if (T.mat5) dst[mslot(PfromO) * C] = (int16_t)clamp_store(vPfromO);  // record-carried (ccj_engine.h rec_only)
-    if (T.mat5) dst[mslot(PLmloop00) * C] = (int16_t)clamp_store(vPLm00);  // record-carried (ccj_engine.h rec_only)
-    dst[mslot(PLmloop01) * C] = (int16_t)clamp_store(vPLm01);
-    if (T.mat5) dst[mslot(PLmloop10) * C] = (int16_t)clamp_store(vPLm10);  // record-carried (ccj_engine.h rec_only)
-    if (T.mat5) dst[mslot(PRmloop00) * C] = (int16_t)clamp_store(vPRm00);  // record-carried (ccj_engine.h rec_only)
-    dst[mslot(PRmloop01) * C] = (int16_t)clamp_store(vPRm01);
-    dst[mslot(PRmloop10) * C] = (int16_t)clamp_store(vPRm10);
+    // (PLmloop00/01/10 and PRmloop00/01/10 are tables, ccj_mloop2d.h: the fill writes none of their
+    // d4 slots; ccjk_tab_slots fills them after the fill where a reader wants them in d4)
     if (T.mat5) dst[mslot(PMmloop00) * C] = (int16_t)clamp_store(vPMm00);  // record-carried (ccj_engine.h rec_only)
     dst[mslot(PMmloop01) * C] = (int16_t)clamp_store(vPMm01);
     if (T.mat5) dst[mslot(PMmloop10) * C] = (int16_t)clamp_store(vPMm10);  // record-carried (ccj_engine.h rec_only)
@@ -1908,10 +1926,9 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     // its pair can pair); in sharded fills the other ranks' cells get both from k_unpack
     if (!copies) return;
 #ifndef CCJ_ABLATE_NOREC  // timing only: no loop-record stores (the split loops then read stale records)
-    write_records(T, Lt.lr, C, (unsigned)(a * Mt) + L0, clamp_store(vPLm00), clamp_store(vPMm00), clamp_store(vPOm00),
-                  clamp_store(vPfromL), clamp_store(vPfromO), clamp_store(vPLm10), clamp_store(vPfromMp),
-                  clamp_store(vPK), clamp_store(vPRm00), clamp_store(vPfromR), imin(sPL, sPR), clamp_store(vPMm10),
-                  clamp_store(vPOm10));
+    write_records(T, Lt.lr, C, (unsigned)(a * Mt) + L0, clamp_store(vPMm00), clamp_store(vPOm00), clamp_store(vPfromL),
+                  clamp_store(vPfromO), clamp_store(vPfromMp), clamp_store(vPK), clamp_store(vPfromR), imin(sPL, sPR),
+                  clamp_store(vPMm10), clamp_store(vPOm10));
 #endif
 #ifdef CCJ_ABLATE_NOCOPY
     return;  // timing only: no interior-loop copies (k_iloop then reads stale values)
@@ -1930,6 +1947,16 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 __global__ __launch_bounds__(512) void k_level4d(DevTables T, int t, int wavesPerA, int split, int G, int rank, int nblk, int copies) {
     level4d_body<false>(T, t, wavesPerA, split, G, rank, nblk, copies);
 }
+// The leader launch is held at 3 waves per SIMD.  Since the PL / PR multiloop terms left, it would
+// fit 4 (123 VGPRs instead of 132), and 4 measured slower at n=200: step 33.3 ms against 32.5 ms
+// with 3, and faster at n=400, 570 ms against 583 ms (parent: 34.4 / 627 ms; DESIGN.md §4,
+// profiles/mloop2d_ab.txt).  -DCCJ_LEAD_WAVES=0 lifts the limit, =k sets another (A/B builds).
+#ifndef CCJ_LEAD_WAVES
+#define CCJ_LEAD_WAVES 3
+#endif
+#if CCJ_LEAD_WAVES > 0
+__attribute__((amdgpu_waves_per_eu(CCJ_LEAD_WAVES, CCJ_LEAD_WAVES)))
+#endif
 __global__ __launch_bounds__(512) void k_level4d_lead(DevTables T, int t, int wavesPerA, int split, int G, int rank, int nblk,
                                                       int copies) {
     level4d_body<true>(T, t, wavesPerA, split, G, rank, nblk, copies);
@@ -1952,8 +1979,10 @@ extern "C" int ccjk_precompute_ie(const DevTables *T, void *stream) {
 extern "C" int ccjk_diag2d(const DevTables *T, int sigma, int G, int rank, void *stream) {
     const int nint = T->n - sigma;  // intervals of the span; rank takes i = rank+1, rank+1+G, ...
     const int nb = nint > rank ? (nint - rank + G - 1) / G : 0;
-    if (nb <= 0) return 0;
-    hipLaunchKernelGGL(k_diag2d, dim3(nb), dim3(256), 0, (hipStream_t)stream, *T, sigma, G, rank);
+    // + the span's PL / PR multiloop tables, one wave per interval (every interval on every rank)
+    const int ntab = nint > 0 ? (nint + 3) / 4 : 0;
+    if (nb + ntab <= 0) return 0;
+    hipLaunchKernelGGL(k_diag2d, dim3(nb + ntab), dim3(256), 0, (hipStream_t)stream, *T, sigma, G, rank, nb);
     return (int)hipGetLastError();
 }
 
@@ -2073,7 +2102,8 @@ __global__ __launch_bounds__(256) void k_pack(DevTables T, int t, int G, int r, 
     const LvlDev Lt = T.ld[t];
     const int16_t *src = T.d4 + Lt.lb + (long long)shard_a(xch_own(k, part), G, r) * Mt + c;
 #pragma unroll 2
-    for (int x = 0; x < NMAT4; ++x) send[xch_pos(x, k, c, nmax, Mt)] = src[(long long)mslot(x) * Lt.C];
+    for (int x = 0; x < NMAT4; ++x)  // the six table-carried matrices keep their place in the slice, unused (32767)
+        send[xch_pos(x, k, c, nmax, Mt)] = tab_only(x) ? (int16_t)INTERN_INF : src[(long long)mslot(x) * Lt.C];
 }
 
 __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r, int part, int nmax, const int16_t *recv,
@@ -2102,12 +2132,12 @@ __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r
     const int16_t *sl = recv + (size_t)ro * rstride;
 #pragma unroll
     for (int x = 0; x < NMAT4; ++x) {
+        if (tab_only(x)) continue;  // every rank computes the tables itself (ccj_mloop2d.h)
         v[x] = sl[xch_pos(x, k, c, nmax, Mt)];
         dst[mslot(x) * C] = (int16_t)v[x];
     }
-    write_records(T, Lt.lr, Lt.C, (unsigned)(a * Mt + c), v[PLmloop00], v[PMmloop00], v[POmloop00], v[PfromL], v[PfromO],
-                  v[PLmloop10], v[PfromMprime], v[PK], v[PRmloop00], v[PfromR], imin(v[PL], v[PR]), v[PMmloop10],
-                  v[POmloop10]);
+    write_records(T, Lt.lr, Lt.C, (unsigned)(a * Mt + c), v[PMmloop00], v[POmloop00], v[PfromL], v[PfromO], v[PfromMprime],
+                  v[PK], v[PfromR], imin(v[PL], v[PR]), v[PMmloop10], v[POmloop10]);
     if (ptype(T, i, j) > 0) T.d4x[X.lbx + (long long)a * Mt + (i - 1) * m - (((i - 1) * (i - 2)) >> 1) + h] = (int16_t)v[PL];
     if (ptype(T, kk, l) > 0) {
         const int q = i + h - 1;
@@ -2201,7 +2231,9 @@ __global__ __launch_bounds__(256) void k_canon(DevTables T, int x, int t, const 
     const int i = c - Gh + 1, j = i + a, k = j + h + 2, l = k + (t - a);
     const long long u = k - (j + 2);
     const long long pos = offij[(long long)i * (n + 1) + j] + u * (n + 1) - u * (2LL * j + 3 + u) / 2 + (l - k);
-    out[pos] = (int16_t)((!T.mat5 && rec_only(x)) ? rec_get(T, x, L, cidx) : (int)T.d4[L.lb + (long long)mslot(x) * L.C + cidx]);
+    out[pos] = (int16_t)(tab_only(x)                  ? tab_get(T, x, i, j, k, l)
+                         : (!T.mat5 && rec_only(x)) ? rec_get(T, x, L, cidx)
+                                                    : (int)T.d4[L.lb + (long long)mslot(x) * L.C + cidx]);
 }
 
 // the record-carried matrices of level t (ccj_engine.h rec_only), read back from its records into out
@@ -2213,7 +2245,42 @@ __global__ __launch_bounds__(256) void k_mat5(DevTables T, int t, int16_t *out) 
     if (cidx >= (long long)L.C) return;
 #pragma unroll
     for (int x = 0; x < NMAT4; ++x)
-        if (rec_only(x)) out[(long long)(mslot(x) - NMAT_ST) * L.C + cidx] = (int16_t)rec_get(T, x, L, cidx);
+        if (rec_only(x) && !tab_only(x)) out[(long long)(mslot(x) - NMAT_ST) * L.C + cidx] = (int16_t)rec_get(T, x, L, cidx);
+}
+
+// The six table-carried matrices (ccj_mloop2d.h) of level t written out per cell, for readers that
+// want them as 4-D slots (the host mirror; d4 of a context that keeps 22 slots): the three with a
+// stored slot (PLmloop01, PRmloop01, PRmloop10) into out_st[mslot * C + cell], the three with a
+// record-carried slot (PLmloop00, PLmloop10, PRmloop00) into out_rec[(mslot - NMAT_ST) * C + cell]
+// (skipped when out_rec is null).  Runs after the fill: level t has cells of table spans up to t.
+__global__ __launch_bounds__(256) void k_tab_slots(DevTables T, int t, int16_t *out_st, int16_t *out_rec) {
+    const int n = T.n, m = n - t - 2;
+    const LvlDev L = T.ld[t];
+    const int Mt = L.M;
+    const long long cidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (cidx >= (long long)L.C) return;
+    const int a = (int)(cidx / Mt), c = (int)(cidx - (long long)a * Mt);
+    const float tm = 2.0f * m + 1.0f;
+    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
+    h = imax(0, imin(h, m - 1));
+    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
+    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
+    const int Gh = h * m - ((h * (h - 1)) >> 1);
+    const int i = c - Gh + 1, j = i + a, k = j + h + 2, l = k + (t - a);
+#pragma unroll
+    for (int x = PLmloop00; x <= PRmloop10; ++x) {
+        const int16_t v = (int16_t)tab_get(T, x, i, j, k, l);
+        if (!rec_only(x)) out_st[(long long)mslot(x) * L.C + cidx] = v;
+        else if (out_rec) out_rec[(long long)(mslot(x) - NMAT_ST) * L.C + cidx] = v;
+    }
+}
+
+extern "C" int ccjk_tab_slots(const DevTables *T, int t, int16_t *out_st, int16_t *out_rec, void *stream) {
+    const int m = T->n - t - 2;
+    if (m <= 0 || t >= T->nlev) return 0;
+    const long long C = (long long)(t + 1) * (m * (m + 1) / 2);
+    hipLaunchKernelGGL(k_tab_slots, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, out_st, out_rec);
+    return (int)hipGetLastError();
 }
 
 extern "C" int ccjk_mat5(const DevTables *T, int t, int16_t *out, void *stream) {
@@ -2253,7 +2320,7 @@ extern "C" int ccjk_level4d(const DevTables *T, int t, int G, int rank, int copi
     const int threads = split <= 4 ? 256 : 64 * split;
     const int cpb = threads / 64 / split;
     const long blocks = (waves + cpb - 1) / cpb;
-    const size_t shmem = split > 1 ? (size_t)cpb * (split - 1) * 22 * 64 * sizeof(int) : 0;
+    const size_t shmem = split > 1 ? (size_t)cpb * (split - 1) * SPLIT_RED * 64 * sizeof(int) : 0;
     hipLaunchKernelGGL(k_level4d, dim3((unsigned)blocks), dim3(threads), shmem, (hipStream_t)stream, *T, t, wavesPerA, split,
                        G, rank, nblk, copies);
     return (int)hipGetLastError();
@@ -2273,7 +2340,7 @@ extern "C" int ccjk_level4d_lead(const DevTables *T, int t, int G, int rank, voi
     // each leader chunk's scans are split over sp waves of one workgroup: 2, or on the narrow late
     // levels as many as the plain heuristic would give the rank's blocks (level_sched, ccj_engine.h)
     const int sp = level_sched(T->n, t, G, rank, T->split_target, T->g_lo, T->g_hi, nblk).lead_split;
-    const size_t shmem = sp > 1 ? (size_t)(sp - 1) * (LEAD_RED > 22 ? LEAD_RED : 22) * 64 * sizeof(int) : 0;
+    const size_t shmem = sp > 1 ? (size_t)(sp - 1) * (LEAD_RED > SPLIT_RED ? LEAD_RED : SPLIT_RED) * 64 * sizeof(int) : 0;
     hipLaunchKernelGGL(k_level4d_lead, dim3((unsigned)waves), dim3(64 * sp), shmem, (hipStream_t)stream, *T, t, wavesPerA,
                        sp, G, rank, nblk, 1);
     return (int)hipGetLastError();
