@@ -49,12 +49,9 @@ struct DevStore {
     }
     __device__ __forceinline__ int Vtype(int i, int j) const { return T.Vt[(j - i) * rs + i]; }
     __device__ __forceinline__ int raw4(int x, int i, int j, int k, int l) const {
-        if (tab_only(x)) return tab_get(T, x, i, j, k, l);  // PL / PR multiloop family: 2-D table (ccj_mloop2d.h)
         const int t = (j - i) + (l - k), m = n - t - 2, h = k - j - 2, a = j - i;
         const LvlDev L = ld[t];
-        const long long cell = (long long)a * L.M + h * m - ((h * (h - 1)) >> 1) + i - 1;
-        if (!T.mat5 && rec_only(x)) return rec_get(T, x, L, cell);  // record-only matrix (ccj_engine.h)
-        return (int)T.d4[L.lb + (long long)mslot(x) * L.C + cell];
+        return mat4_get(T, x, L, (long long)a * L.M + h * m - ((h * (h - 1)) >> 1) + i - 1, i, j, k, l);
     }
     // the P_P split key k_pterm keeps with the minimum (T.Pk)
     __device__ __forceinline__ unsigned pk(int i, int l) const { return (unsigned)(T.Pk[(l - i) * rs + i] & 0xffffffffull); }

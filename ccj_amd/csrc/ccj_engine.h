@@ -4,8 +4,9 @@
 //   * 4-D gap matrices: level-major.  A cell (i,j,k,l) has a = j-i, g = k-j (>= 2), b = l-k,
 //     level t = a+b, h = g-2.  Level t holds (t+1) blocks (one per a) of M_t = m_t(m_t+1)/2 cells,
 //     m_t = n-t-2, each block a triangle of rows h = 0..m_t-1 of length m_t-h, i fastest.
-//     Within a level the 22 matrices are stored one after another (SoA), so one level is one
-//     contiguous span:  elem(x,t,a,h,i) = LB_t + x*C_t + a*M_t + G_t(h) + (i-1),
+//     Within a level the matrix slots (mslot below: 8 in a lean context, all 22 in a full one) are
+//     stored one after another (SoA), so one level is one contiguous span:
+//     elem(x,t,a,h,i) = LB_t + mslot(x)*C_t + a*M_t + G_t(h) + (i-1),
 //     G_t(h) = h*m_t - h(h-1)/2, C_t = (t+1)*M_t.
 //     Every dependency of a level-t cell lies in levels < t, and lanes of one
 //     wave (same t, a) read shifted neighbours whose offsets differ by a lane-uniform amount,
@@ -21,27 +22,43 @@
 
 namespace ccj {
 
-// The matrices d4 does not store unless DevTables::mat5: those the loop records carry (below; the 5
-// no fill kernel reads back as matrices and the ones the level kernel's stack terms read from the
-// records, rec_get) and, of the six table-carried matrices (ccj_mloop2d.h), PLmloop00, PLmloop10 and
-// PRmloop00.  The other three table-carried ones (PLmloop01, PRmloop01, PRmloop10) keep their stored
-// slots, which the fill does not write: slot order (mslot) is the host mirror's and stays.
-constexpr unsigned REC_MASK = (1u << PfromL) | (1u << PfromR) | (1u << PfromMprime) | (1u << PfromO) | (1u << PLmloop00) |
-                              (1u << PLmloop10) | (1u << PRmloop00) | (1u << PMmloop00) | (1u << PMmloop10) |
-                              (1u << POmloop00) | (1u << POmloop10);
-__host__ __device__ constexpr bool rec_only(int x) { return (REC_MASK >> x) & 1u; }
-constexpr int NMAT_REC = __builtin_popcount(REC_MASK);
-constexpr int NMAT_ST = NMAT4 - NMAT_REC;
-// Storage slot of matrix x inside a level of d4 and of the host mirror: the 11 stored matrices in
-// enum order, then the 11 record-carried ones.  d4 holds slots [0, 11) per level, or all 22 when
-// DevTables::mat5 (band-sharded exchange, a host mirror streamed during the fill); the host mirror
-// always holds 22.  Matrix-major "level element" indices of the exchange API (x*C + a*M + c) are by
-// matrix, not by slot.
-__host__ __device__ constexpr int rec_below(int x) { return __builtin_popcount(REC_MASK & ((1u << x) - 1u)); }
-__host__ __device__ constexpr int mslot(int x) { return rec_only(x) ? NMAT_ST + rec_below(x) : x - rec_below(x); }
-static_assert(NMAT_REC == 11 && mslot(PK) == 0 && mslot(PO) == 4 && mslot(PfromM) == 5 && mslot(POmloop01) == NMAT_ST - 1,
-              "stored slots");
-static_assert(mslot(PfromL) == NMAT_ST && mslot(POmloop10) == NMAT4 - 1, "record-carried slots");
+// Every 4-D matrix has exactly one carrier, the place the fill writes it to and every reader takes it
+// from:
+//   IN_D4  (8): its slot of d4.  The level kernel stores it and later levels read it there.
+//   IN_REC (8): the loop records (RA / RK / RL below; rec_get).  A full context (DevTables::full4:
+//               band-sharded over an exchange, which packs them from d4, or a host mirror streamed
+//               during the fill) stores them in d4 as well and reads them there.
+//   IN_TAB (6): the 2-D tables of the PL / PR multiloop families (ccj_mloop2d.h; tab_get).  The fill
+//               never writes their d4 slots.
+enum Carrier { IN_D4 = 0, IN_REC = 1, IN_TAB = 2 };
+constexpr unsigned REC_MASK = (1u << PfromL) | (1u << PfromR) | (1u << PfromMprime) | (1u << PfromO) | (1u << PMmloop00) |
+                              (1u << PMmloop10) | (1u << POmloop00) | (1u << POmloop10);
+constexpr unsigned D4_MASK = ((1u << NMAT4) - 1u) & ~(REC_MASK | TAB_MASK);
+static_assert((REC_MASK & TAB_MASK) == 0, "one carrier per matrix");
+__host__ __device__ constexpr Carrier carrier(int x) {
+    return (TAB_MASK >> x) & 1u ? IN_TAB : (REC_MASK >> x) & 1u ? IN_REC : IN_D4;
+}
+constexpr int NMAT_D4 = __builtin_popcount(D4_MASK), NMAT_REC = __builtin_popcount(REC_MASK), NMAT_TAB = __builtin_popcount(TAB_MASK);
+// Storage slot of matrix x inside a level of d4 and of the host mirror: the IN_D4 matrices in enum
+// order, then IN_REC, then IN_TAB.  d4 holds slots [0, NMAT_D4) per level, or all 22 in a full
+// context; the host mirror always holds 22 (ccjk_expand writes out what d4 lacks).  Matrix-major
+// "level element" indices of the exchange API (x*C + a*M + c) are by matrix, not by slot.
+__host__ __device__ constexpr int mslot(int x) {
+    const Carrier c = carrier(x);
+    const unsigned cls = c == IN_D4 ? D4_MASK : c == IN_REC ? REC_MASK : TAB_MASK;
+    const int first = c == IN_D4 ? 0 : c == IN_REC ? NMAT_D4 : NMAT_D4 + NMAT_REC;
+    return first + __builtin_popcount(cls & ((1u << x) - 1u));
+}
+static_assert(NMAT_D4 == 8 && NMAT_REC == 8 && NMAT_TAB == 6 && NMAT_D4 + NMAT_REC + NMAT_TAB == NMAT4, "the partition");
+static_assert(carrier(PK) == IN_D4 && mslot(PK) == 0 && mslot(PO) == 4 && mslot(PfromM) == 5 && carrier(POmloop01) == IN_D4 &&
+                  mslot(POmloop01) == NMAT_D4 - 1,
+              "d4 slots");
+static_assert(carrier(PfromL) == IN_REC && mslot(PfromL) == NMAT_D4 && carrier(POmloop10) == IN_REC &&
+                  mslot(POmloop10) == NMAT_D4 + NMAT_REC - 1,
+              "record-carried slots");
+static_assert(carrier(PLmloop00) == IN_TAB && mslot(PLmloop00) == NMAT_D4 + NMAT_REC && carrier(PRmloop10) == IN_TAB &&
+                  mslot(PRmloop10) == NMAT4 - 1,
+              "table-carried slots");
 
 constexpr int IE_U = 29;  // u1,u2 in [0,28] for pseudoknot interior loops (pseudo_loop.cc:694-806)
 #ifndef CCJ_ILB
@@ -238,7 +255,7 @@ struct DevTables {
     uint2 *il, *ilm;               // il: pair (p,p+w) closes the loop (PL, PR); ilm: pair encloses (PM)
     int16_t *dummy;                // n+64 values 32767: target of the null entries
     const uint32_t *items;         // k_iloop work items (role << 30 | f1 << 20 | f2 << 10 | chunk)
-    int mat5;                      // 1: the 5 record-only matrices are stored in d4 too (22 slots per level, mslot)
+    int full4;                     // 1: a full context, d4 has all 22 slots per level (mslot); 0: the NMAT_D4 first
     uint32_t *ilseg, *ilmseg;      // [pair][IL_SEG]
     int *err;                      // device error word
     // split-point sharing (above): levels [g_lo, g_hi) share; partial-record ring of SHARE_R
@@ -257,12 +274,9 @@ struct DevTables {
     long long accC;
 };
 
-// The record-carried matrices (rec_only and not tab_only) live only in the loop records (RA / RK /
-// RL), unless DevTables::mat5: the level kernel skips their d4 stores and d4 has no slots for them
-// (DESIGN.md §3).  rec_get reads one from the records of the cell at in-level offset cell (a*M + G(h)
-// + i-1); k_mat5 writes a level's into a scratch buffer for the host mirror.
 __device__ __forceinline__ int rlo16(unsigned w) { return (int)(int16_t)(w & 0xffffu); }
 __device__ __forceinline__ int rhi16(unsigned w) { return (int)(int16_t)(w >> 16); }
+// an IN_REC matrix from the records of the cell at in-level offset cell (a*M + G(h) + i-1)
 __device__ __forceinline__ int rec_get(const DevTables &T, int x, const LvlDev &L, long long cell) {
     const rec_t *rp = T.rec + L.lr;
     if (x == PfromR) return rhi16(T.rk[(L.lr >> 1) + cell].x);  // RK: Mm00|fR, PLR|K
@@ -279,12 +293,31 @@ __device__ __forceinline__ int rec_get(const DevTables &T, int x, const LvlDev &
         default: return rlo16(r.z);  // PfromMprime
     }
 }
-// A table-carried matrix (tab_only, ccj_mloop2d.h) at cell (i,j,k,l): every reader outside the fill
-// takes the six from here, whatever d4 holds.
+// an IN_TAB matrix at cell (i,j,k,l)
 __device__ __forceinline__ int tab_get(const DevTables &T, int x, int i, int j, int k, int l) {
     const int ti = tab_index(x);
     const int w = ti < 3 ? j - i : l - k, p = ti < 3 ? i : k;
     return (int)T.tab[(long long)ti * T.tabN + w * T.rs + p];
+}
+
+// The one read of matrix x at cell (i,j,k,l) of level L outside the fill's own hot loops (hashes,
+// traceback, host mirror): by carrier; cell = a*M + G(h) + i-1.
+__device__ __forceinline__ int mat4_get(const DevTables &T, int x, const LvlDev &L, long long cell, int i, int j, int k, int l) {
+    if (carrier(x) == IN_TAB) return tab_get(T, x, i, j, k, l);
+    if (carrier(x) == IN_REC && !T.full4) return rec_get(T, x, L, cell);
+    return (int)T.d4[L.lb + (long long)mslot(x) * L.C + cell];
+}
+
+// Row h of in-block cell c (0 <= c < m(m+1)/2) of a level with m rows: the largest h with
+// G(h) = h*m - h(h-1)/2 <= c.  Gh = G(h), so the cell's i is c - Gh + 1.
+__device__ __forceinline__ int cell_row(int c, int m, int &Gh) {
+    const float tm = 2.0f * m + 1.0f;
+    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
+    h = imax(0, imin(h, m - 1));
+    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
+    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
+    Gh = h * m - ((h * (h - 1)) >> 1);
+    return h;
 }
 
 // element offset of cell (a,h,i) of matrix x inside level t of the host mirror (relative to lv_offh[t])
@@ -393,6 +426,5 @@ int ccjk_ptail_unpack(const ccj::DevTables *T, int sigma, const int16_t *recv, s
 int ccjk_items(const ccj::DevTables *T, int G, int rank, int simulate, long long *counts, const long long *offs,
                uint32_t *items, int pass, void *stream);
 int ccjk_canon(const ccj::DevTables *T, int x, const long long *offij, int16_t *out, void *stream);
-int ccjk_mat5(const ccj::DevTables *T, int t, int16_t *out, void *stream);
-int ccjk_tab_slots(const ccj::DevTables *T, int t, int16_t *out_st, int16_t *out_rec, void *stream);
+int ccjk_expand(const ccj::DevTables *T, int t, int first_slot, int16_t *out, void *stream);
 }

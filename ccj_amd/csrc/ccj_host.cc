@@ -121,8 +121,8 @@ struct ccj_ctx {
     std::vector<int64_t> lv_offh;       // element offset of each level in the host mirror (NMAT4 slots)
     int64_t ncell = 0;                  // cells of the 4-D state per matrix, C(n+1, 4)
     int64_t total4 = 0;                 // elements of d4: nm4 * ncell
-    int nm4 = NMAT_ST;                  // matrix slots per level in d4 (NMAT4 when T.mat5; ccj_engine.h mslot)
-    bool mat5 = false;                  // the record-carried matrices stored in d4 too (DevTables::mat5)
+    bool full4 = false;                 // a full context: d4 has all 22 slots per level (DevTables::full4)
+    int nm4 = NMAT_D4;                  // matrix slots per level in d4 (NMAT4 when full4; ccj_engine.h mslot)
     int nlev = 0;                       // levels with cells (0..n-3)
 
     // device
@@ -778,11 +778,12 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     for (size_t x = 31; x < c->lx.size(); ++x) c->lx[x] = (int)(c->prm.lxc * log((double)x / 30.));
     c->rs = n + 2;
 
-    // level layout.  d4 stores 11 matrix slots per level, or all 22 (mat5) where the band-sharded
-    // exchange packs them or a host mirror streams them during the fill (ccj_engine.h mslot); the
-    // host mirror always has 22
-    c->mat5 = (c->world > 1 && !c->simulate) || c->overlap || (getenv("CCJ_MAT5") && atoi(getenv("CCJ_MAT5")) != 0);
-    c->nm4 = c->mat5 ? NMAT4 : NMAT_ST;
+    // level layout.  d4 has the NMAT_D4 slots per level the fill writes, or all 22 (a full context)
+    // where the band-sharded exchange packs them or a host mirror streams them during the fill
+    // (ccj_engine.h carrier); CCJ_D4_FULL=1 makes any context full (A/B timing).  The host mirror
+    // always has 22
+    c->full4 = (c->world > 1 && !c->simulate) || c->overlap || (getenv("CCJ_D4_FULL") && atoi(getenv("CCJ_D4_FULL")) != 0);
+    c->nm4 = c->full4 ? NMAT4 : NMAT_D4;
     c->lv_host.assign(std::max(n, 1), LevelDesc{nullptr, 0, 0, 0, 0});
     c->lv_off.assign(std::max(n, 1), 0);
     c->lv_offh.assign(std::max(n, 1), 0);
@@ -1052,9 +1053,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.ilm = c->d_ilm;
     T.dummy = c->d_dummy;
     T.items = c->d_items;
-    // the exchange packs all 22 matrices from d4, a mirror streamed during the fill copies them;
-    // CCJ_MAT5=1 stores them in every fill (A/B timing)
-    T.mat5 = c->mat5 ? 1 : 0;
+    T.full4 = c->full4 ? 1 : 0;
     T.ilseg = c->d_ilseg;
     T.ilmseg = c->d_ilmseg;
     T.err = c->d_err;
@@ -1144,6 +1143,13 @@ static int pterm_launch(const ccj_ctx *c, int lev, hipStream_t s) {
     return 0;
 }
 
+// A full context's d4 has the host mirror's layout except that the fill leaves the IN_TAB slots of
+// every level unwritten: write level t's from the tables, in front of a copy to the mirror.
+static int expand_tab_slots(const ccj_ctx *c, int t, hipStream_t s) {
+    constexpr int first = NMAT_D4 + NMAT_REC;
+    return ccjk_expand(&c->T, t, first, c->d4 + c->lv_off[t] + (size_t)first * c->lv_host[t].C, s);
+}
+
 static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     if (!c) return CCJ_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1161,7 +1167,8 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     HIPCHK(c, (hipError_t)ccjk_build_il(&c->T, st));
     HIPCHK(c, hipEventRecord(c->ev_pre, st));
     // Four streams:
-    //   st_d : k_diag2d(s)  needs P(s) (p_done) and spans < s (stream order)
+    //   st_d : k_diag2d(s)  needs P(s) (p_done) and spans < s (stream order); with join_diag (below)
+    //                       it runs on st_il instead, behind k_iloop(s+1), and st_d stays empty
     //   st_il: k_iloop(t)   needs 4-D levels <= t-3 (lev_done[t-3]; the dt = 2 term is in k_level4d)
     //   st   : k_level4d(t) needs level t-1 (stream order), k_iloop(t), k_diag2d(t-1)
     //   st_p : k_pterm(s)   needs PK levels <= s-3 (lev_done[s-3])
@@ -1366,15 +1373,14 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - enq0).count());
     if (c->overlap && c->h4) {
         // stream each finished level to the pinned host mirror while later levels run.  Its six
-        // table-carried slots (ccj_mloop2d.h) are written first, from table spans <= s (k_diag2d(s));
-        // enqueued here because every event st_copy waits on must have been recorded
+        // table-carried slots are written first, from table spans <= s (k_diag2d(s)); enqueued here
+        // because every event st_copy waits on must have been recorded
         for (int s = 0; s < c->nlev; ++s) {
             HIPCHK(c, hipStreamWaitEvent(c->st_copy, lvl_full[s], 0));
             HIPCHK(c, hipStreamWaitEvent(c->st_copy, c->dg_done[s], 0));
-            int16_t *lv = c->d4 + c->lv_off[s];
-            HIPCHK(c, (hipError_t)ccjk_tab_slots(&c->T, s, lv, lv + (size_t)NMAT_ST * c->lv_host[s].C, c->st_copy));
+            HIPCHK(c, (hipError_t)expand_tab_slots(c, s, c->st_copy));
             const size_t bytes = (size_t)NMAT4 * c->lv_host[s].C * sizeof(int16_t);
-            HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], lv, bytes, hipMemcpyDeviceToHost, c->st_copy));
+            HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], c->d4 + c->lv_off[s], bytes, hipMemcpyDeviceToHost, c->st_copy));
         }
     }
     // join: the fill ends when the last level (every rank's part of it) and the last span are done
@@ -1515,29 +1521,24 @@ extern "C" int ccj_sync_host(ccj_ctx *c) {
         const size_t hbytes = (size_t)NMAT4 * c->ncell * sizeof(int16_t);
         if (!c->h4 && hipHostMalloc(&c->h4, hbytes, hipHostMallocDefault) != hipSuccess)
             return set_err(c, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", hbytes * 1e-9);
-        if (c->mat5) {  // d4 has the mirror's layout; the fill left the six table-carried slots unwritten
-            for (int t = 0; t < c->nlev; ++t) {
-                int16_t *lv = c->d4 + c->lv_off[t];
-                HIPCHK(c, (hipError_t)ccjk_tab_slots(&c->T, t, lv, lv + (size_t)NMAT_ST * c->lv_host[t].C, c->st));
-            }
+        if (c->full4) {  // d4 has the mirror's layout
+            for (int t = 0; t < c->nlev; ++t) HIPCHK(c, (hipError_t)expand_tab_slots(c, t, c->st));
             HIPCHK(c, hipStreamSynchronize(c->st));
             HIPCHK(c, hipMemcpy(c->h4, c->d4, hbytes, hipMemcpyDeviceToHost));
-        } else {  // per level: the NMAT_ST stored slots, then the record-carried ones read back from the records
+        } else {  // per level: the NMAT_D4 slots of d4, then the other matrices written out into a scratch
+            constexpr int nexp = NMAT4 - NMAT_D4;
             size_t cmax = 0;
             for (int t = 0; t < c->nlev; ++t) cmax = std::max(cmax, (size_t)c->lv_host[t].C);
             int16_t *scr = nullptr;
-            if (hipMalloc(&scr, (size_t)NMAT_REC * cmax * sizeof(int16_t)) != hipSuccess)
-                return set_err(c, CCJ_E_OOM, "ccj_sync_host: device scratch of %.2f GB", NMAT_REC * cmax * 2e-9);
+            if (hipMalloc(&scr, (size_t)nexp * cmax * sizeof(int16_t)) != hipSuccess)
+                return set_err(c, CCJ_E_OOM, "ccj_sync_host: device scratch of %.2f GB", nexp * cmax * 2e-9);
             int rc = CCJ_OK;
             for (int t = 0; t < c->nlev && rc == CCJ_OK; ++t) {
                 const size_t C = (size_t)c->lv_host[t].C;
-                // the six table-carried matrices: three into their (otherwise unwritten) stored slots of
-                // d4, three into the scratch beside the record-carried ones
-                if (ccjk_tab_slots(&c->T, t, c->d4 + c->lv_off[t], scr, c->st) != 0 || ccjk_mat5(&c->T, t, scr, c->st) != 0 ||
-                    hipStreamSynchronize(c->st) != hipSuccess ||
-                    hipMemcpy(c->h4 + c->lv_offh[t], c->d4 + c->lv_off[t], (size_t)NMAT_ST * C * sizeof(int16_t),
+                if (ccjk_expand(&c->T, t, NMAT_D4, scr, c->st) != 0 || hipStreamSynchronize(c->st) != hipSuccess ||
+                    hipMemcpy(c->h4 + c->lv_offh[t], c->d4 + c->lv_off[t], (size_t)NMAT_D4 * C * sizeof(int16_t),
                               hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(c->h4 + c->lv_offh[t] + (size_t)NMAT_ST * C, scr, (size_t)NMAT_REC * C * sizeof(int16_t),
+                    hipMemcpy(c->h4 + c->lv_offh[t] + (size_t)NMAT_D4 * C, scr, (size_t)nexp * C * sizeof(int16_t),
                               hipMemcpyDeviceToHost) != hipSuccess)
                     rc = set_err(c, CCJ_E_HIP, "ccj_sync_host: mirror copy of level %d failed", t);
             }

@@ -1295,13 +1295,8 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     if (split == 1 && c_raw >= Mt) return;
     const bool lane_ok = wave_ok && c_raw < Mt;
     const int c = imin(c_raw, Mt - 1);  // idle lanes shadow the last cell (valid reads, no store)
-    // row h: largest h with G(h) = h*m - h(h-1)/2 <= c
-    const float tm = 2.0f * m + 1.0f;
-    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
-    h = imax(0, imin(h, m - 1));
-    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
-    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
-    const int Gh = h * m - ((h * (h - 1)) >> 1);
+    int Gh;
+    const int h = cell_row(c, m, Gh);
     const int b = t - a;
     const int i = c - Gh + 1;
     const int g = h + 2;
@@ -1794,7 +1789,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             const LvlDev L = LD[t - 1];
             const int16_t *lp = D4 + L.lb;
             if (b >= 1) vPMm01 = imin(vPMm01, LDX(lp, L, PMmloop01, a * L.M + m + 1, L0) + cp);       // (i,j,k+1,l)
-            // PMmloop10 from the RL record (d4 does not store it: ccj_engine.h rec_only)
+            // PMmloop10 from the RL record (IN_REC, ccj_engine.h carrier: not read from d4)
             if (a >= 1) vPMm10 = imin(vPMm10, lo16(T.rec[L.lr + (unsigned)(L.C + (a - 1) * L.M + m + 1) + L0].y) + cp);  // (i,j-1,k,l)
         }
     }
@@ -1809,7 +1804,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     const LvlDev L2 = LD[t >= 2 ? t - 2 : 0];
     const int16_t *lp2 = D4 + L2.lb;
     // the record-carried matrices of those neighbours (PfromL, PfromR, PMmloop10, POmloop10, PfromO;
-    // ccj_engine.h rec_only) from their loop records: one 12-byte load per cell
+    // IN_REC, ccj_engine.h carrier) from their loop records: one 12-byte load per cell
     const rec_t *rp2 = T.rec + L2.lr;
     // own slots of level t: k_iloop(t) left the interior-loop minima of PL/PR/PM there
     const LvlDev Lt = LD[t];
@@ -1909,19 +1904,19 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     dst[mslot(PR) * C] = (int16_t)sPR;
     dst[mslot(PM) * C] = (int16_t)sPM;
     dst[mslot(PO) * C] = (int16_t)sPO;
-    if (T.mat5) dst[mslot(PfromL) * C] = (int16_t)clamp_store(vPfromL);  // record-carried (ccj_engine.h rec_only)
-    if (T.mat5) dst[mslot(PfromR) * C] = (int16_t)clamp_store(vPfromR);  // record-carried (ccj_engine.h rec_only)
+    // the IN_D4 matrices always, the IN_REC ones only where d4 has their slots (ccj_engine.h carrier;
+    // the IN_TAB ones never: ccjk_expand writes them out after the fill where a reader wants them)
+    if (T.full4) dst[mslot(PfromL) * C] = (int16_t)clamp_store(vPfromL);
+    if (T.full4) dst[mslot(PfromR) * C] = (int16_t)clamp_store(vPfromR);
     dst[mslot(PfromM) * C] = (int16_t)clamp_store(vPfromM);
-    if (T.mat5) dst[mslot(PfromMprime) * C] = (int16_t)clamp_store(vPfromMp);  // record-carried (ccj_engine.h rec_only)
-    if (T.mat5) dst[mslot(PfromO) * C] = (int16_t)clamp_store(vPfromO);  // record-carried (ccj_engine.h rec_only)
-    // (PLmloop00/01/10 and PRmloop00/01/10 are tables, ccj_mloop2d.h: the fill writes none of their
-    // d4 slots; ccjk_tab_slots fills them after the fill where a reader wants them in d4)
-    if (T.mat5) dst[mslot(PMmloop00) * C] = (int16_t)clamp_store(vPMm00);  // record-carried (ccj_engine.h rec_only)
+    if (T.full4) dst[mslot(PfromMprime) * C] = (int16_t)clamp_store(vPfromMp);
+    if (T.full4) dst[mslot(PfromO) * C] = (int16_t)clamp_store(vPfromO);
+    if (T.full4) dst[mslot(PMmloop00) * C] = (int16_t)clamp_store(vPMm00);
     dst[mslot(PMmloop01) * C] = (int16_t)clamp_store(vPMm01);
-    if (T.mat5) dst[mslot(PMmloop10) * C] = (int16_t)clamp_store(vPMm10);  // record-carried (ccj_engine.h rec_only)
-    if (T.mat5) dst[mslot(POmloop00) * C] = (int16_t)clamp_store(vPOm00);  // record-carried (ccj_engine.h rec_only)
+    if (T.full4) dst[mslot(PMmloop10) * C] = (int16_t)clamp_store(vPMm10);
+    if (T.full4) dst[mslot(POmloop00) * C] = (int16_t)clamp_store(vPOm00);
     dst[mslot(POmloop01) * C] = (int16_t)clamp_store(vPOm01);
-    if (T.mat5) dst[mslot(POmloop10) * C] = (int16_t)clamp_store(vPOm10);  // record-carried (ccj_engine.h rec_only)
+    if (T.full4) dst[mslot(POmloop10) * C] = (int16_t)clamp_store(vPOm10);
     // loop records and interior-loop copies (the copies only where a later k_iloop can read them:
     // its pair can pair); in sharded fills the other ranks' cells get both from k_unpack
     if (!copies) return;
@@ -2090,7 +2085,7 @@ extern "C" int ccjk_iloop(const DevTables *T, int t, long long first_item, int n
 // each part is ONE all-gather of equal slices.  k_unpack: every cell of the other ranks' blocks of the
 // part from the gathered slices (rank r's at recv + r * rstride) back into the level layout, plus its
 // loop records and interior-loop copies (what k_level4d writes for its own cells).  The slices carry
-// all 22 matrices, the record-only five included (exchange fills keep T.mat5 = 1), so the records are
+// all 22 matrices, the IN_REC ones included (an exchange context is full, T.full4), so the records are
 // rebuilt from them.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pack(DevTables T, int t, int G, int r, int part, int nmax, int16_t *send) {
@@ -2103,7 +2098,7 @@ __global__ __launch_bounds__(256) void k_pack(DevTables T, int t, int G, int r, 
     const int16_t *src = T.d4 + Lt.lb + (long long)shard_a(xch_own(k, part), G, r) * Mt + c;
 #pragma unroll 2
     for (int x = 0; x < NMAT4; ++x)  // the six table-carried matrices keep their place in the slice, unused (32767)
-        send[xch_pos(x, k, c, nmax, Mt)] = tab_only(x) ? (int16_t)INTERN_INF : src[(long long)mslot(x) * Lt.C];
+        send[xch_pos(x, k, c, nmax, Mt)] = carrier(x) == IN_TAB ? (int16_t)INTERN_INF : src[(long long)mslot(x) * Lt.C];
 }
 
 __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r, int part, int nmax, const int16_t *recv,
@@ -2116,12 +2111,8 @@ __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r
     xch_src(a, G, ro, pa, k);
     if (ro == r || pa != part) return;  // own cell (k_level4d wrote it with its records and copies), or the other part
     const int c = (int)(gc - (long long)a * Mt);
-    const float tm = 2.0f * m + 1.0f;
-    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
-    h = imax(0, imin(h, m - 1));
-    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
-    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
-    const int Gh = h * m - ((h * (h - 1)) >> 1);
+    int Gh;
+    const int h = cell_row(c, m, Gh);
     const int i = c - Gh + 1, b = t - a;
     const int j = i + a, kk = j + h + 2, l = kk + b;
     const LvlDev Lt = T.ld[t];
@@ -2132,7 +2123,7 @@ __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r
     const int16_t *sl = recv + (size_t)ro * rstride;
 #pragma unroll
     for (int x = 0; x < NMAT4; ++x) {
-        if (tab_only(x)) continue;  // every rank computes the tables itself (ccj_mloop2d.h)
+        if (carrier(x) == IN_TAB) continue;  // every rank computes the tables itself (ccj_mloop2d.h)
         v[x] = sl[xch_pos(x, k, c, nmax, Mt)];
         dst[mslot(x) * C] = (int16_t)v[x];
     }
@@ -2187,7 +2178,7 @@ extern "C" int ccjk_ptail_unpack(const DevTables *T, int sigma, const int16_t *r
 extern "C" int ccjk_pack(const DevTables *T, int t, int G, int r, int part, int nmax, int16_t *send, void *stream) {
     const int m = T->n - t - 2;
     if (m <= 0) return 0;
-    if (xch_pcount(t, G, r, part) > nmax) return (int)hipErrorInvalidValue;
+    if (xch_pcount(t, G, r, part) > nmax || !T->full4) return (int)hipErrorInvalidValue;  // packs all of d4's 22 slots
     const long long cells = (long long)xch_pcount(t, G, r, part) * (m * (m + 1) / 2);
     if (cells <= 0) return 0;
     hipLaunchKernelGGL(k_pack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, G, r, part, nmax,
@@ -2200,8 +2191,8 @@ extern "C" int ccjk_unpack(const DevTables *T, int t, int G, int r, int part, in
     const int m = T->n - t - 2;
     if (m <= 0) return 0;
     // the records of the other ranks' cells are rebuilt from the slices, which must carry all 22
-    // matrices: without T.mat5 the five record-only matrices are not in d4 (k_pack would ship stale ones)
-    if (!recv || !T->mat5) return (int)hipErrorInvalidValue;
+    // matrices: a lean d4 has no slots for the IN_REC ones (k_pack would read past the level)
+    if (!recv || !T->full4) return (int)hipErrorInvalidValue;
     const long long cells = (long long)(t + 1) * (m * (m + 1) / 2);
     if (xch_nmax(t, G, part) > nmax) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_unpack, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, G, r, part, nmax,
@@ -2222,72 +2213,39 @@ __global__ __launch_bounds__(256) void k_canon(DevTables T, int x, int t, const 
     const long long cidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (cidx >= (long long)L.C) return;
     const int a = (int)(cidx / Mt), c = (int)(cidx - (long long)a * Mt);
-    const float tm = 2.0f * m + 1.0f;
-    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
-    h = imax(0, imin(h, m - 1));
-    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
-    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
-    const int Gh = h * m - ((h * (h - 1)) >> 1);
+    int Gh;
+    const int h = cell_row(c, m, Gh);
     const int i = c - Gh + 1, j = i + a, k = j + h + 2, l = k + (t - a);
     const long long u = k - (j + 2);
     const long long pos = offij[(long long)i * (n + 1) + j] + u * (n + 1) - u * (2LL * j + 3 + u) / 2 + (l - k);
-    out[pos] = (int16_t)(tab_only(x)                  ? tab_get(T, x, i, j, k, l)
-                         : (!T.mat5 && rec_only(x)) ? rec_get(T, x, L, cidx)
-                                                    : (int)T.d4[L.lb + (long long)mslot(x) * L.C + cidx]);
+    out[pos] = (int16_t)mat4_get(T, x, L, cidx, i, j, k, l);
 }
 
-// the record-carried matrices of level t (ccj_engine.h rec_only), read back from its records into out
-// (slots NMAT_ST.. of the level's host-mirror layout, mslot), for a host mirror of a context without
-// them in d4
-__global__ __launch_bounds__(256) void k_mat5(DevTables T, int t, int16_t *out) {
-    const LvlDev L = T.ld[t];
-    const long long cidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (cidx >= (long long)L.C) return;
-#pragma unroll
-    for (int x = 0; x < NMAT4; ++x)
-        if (rec_only(x) && !tab_only(x)) out[(long long)(mslot(x) - NMAT_ST) * L.C + cidx] = (int16_t)rec_get(T, x, L, cidx);
-}
-
-// The six table-carried matrices (ccj_mloop2d.h) of level t written out per cell, for readers that
-// want them as 4-D slots (the host mirror; d4 of a context that keeps 22 slots): the three with a
-// stored slot (PLmloop01, PRmloop01, PRmloop10) into out_st[mslot * C + cell], the three with a
-// record-carried slot (PLmloop00, PLmloop10, PRmloop00) into out_rec[(mslot - NMAT_ST) * C + cell]
-// (skipped when out_rec is null).  Runs after the fill: level t has cells of table spans up to t.
-__global__ __launch_bounds__(256) void k_tab_slots(DevTables T, int t, int16_t *out_st, int16_t *out_rec) {
+// Slots [first_slot, NMAT4) of level t (ccj_engine.h mslot; first_slot >= NMAT_D4) written out per cell
+// through mat4_get, to out[(slot - first_slot) * C + cell]: what d4 lacks of the level's host-mirror
+// layout.  Runs after the fill, or once k_diag2d(t) is done: level t has cells of table spans up to t.
+__global__ __launch_bounds__(256) void k_expand(DevTables T, int t, int first_slot, int16_t *out) {
     const int n = T.n, m = n - t - 2;
     const LvlDev L = T.ld[t];
     const int Mt = L.M;
     const long long cidx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (cidx >= (long long)L.C) return;
     const int a = (int)(cidx / Mt), c = (int)(cidx - (long long)a * Mt);
-    const float tm = 2.0f * m + 1.0f;
-    int h = (int)((tm - sqrtf(tm * tm - 8.0f * (float)c)) * 0.5f);
-    h = imax(0, imin(h, m - 1));
-    while (h > 0 && h * m - ((h * (h - 1)) >> 1) > c) --h;
-    while (h + 1 < m && (h + 1) * m - (((h + 1) * h) >> 1) <= c) ++h;
-    const int Gh = h * m - ((h * (h - 1)) >> 1);
+    int Gh;
+    const int h = cell_row(c, m, Gh);
     const int i = c - Gh + 1, j = i + a, k = j + h + 2, l = k + (t - a);
 #pragma unroll
-    for (int x = PLmloop00; x <= PRmloop10; ++x) {
-        const int16_t v = (int16_t)tab_get(T, x, i, j, k, l);
-        if (!rec_only(x)) out_st[(long long)mslot(x) * L.C + cidx] = v;
-        else if (out_rec) out_rec[(long long)(mslot(x) - NMAT_ST) * L.C + cidx] = v;
-    }
+    for (int x = 0; x < NMAT4; ++x)
+        if (carrier(x) != IN_D4 && mslot(x) >= first_slot)
+            out[(long long)(mslot(x) - first_slot) * L.C + cidx] = (int16_t)mat4_get(T, x, L, cidx, i, j, k, l);
 }
 
-extern "C" int ccjk_tab_slots(const DevTables *T, int t, int16_t *out_st, int16_t *out_rec, void *stream) {
+extern "C" int ccjk_expand(const DevTables *T, int t, int first_slot, int16_t *out, void *stream) {
     const int m = T->n - t - 2;
+    if (first_slot < NMAT_D4 || first_slot >= NMAT4 || !out) return (int)hipErrorInvalidValue;
     if (m <= 0 || t >= T->nlev) return 0;
     const long long C = (long long)(t + 1) * (m * (m + 1) / 2);
-    hipLaunchKernelGGL(k_tab_slots, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, out_st, out_rec);
-    return (int)hipGetLastError();
-}
-
-extern "C" int ccjk_mat5(const DevTables *T, int t, int16_t *out, void *stream) {
-    const int m = T->n - t - 2;
-    if (m <= 0 || t >= T->nlev) return 0;
-    const long long C = (long long)(t + 1) * (m * (m + 1) / 2);
-    hipLaunchKernelGGL(k_mat5, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, out);
+    hipLaunchKernelGGL(k_expand, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T, t, first_slot, out);
     return (int)hipGetLastError();
 }
 

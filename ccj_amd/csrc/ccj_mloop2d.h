@@ -15,11 +15,10 @@
 
 namespace ccj {
 
+// the six table-carried matrices (ccj_engine.h carrier: IN_TAB)
 constexpr unsigned TAB_MASK = (1u << PLmloop00) | (1u << PLmloop01) | (1u << PLmloop10) | (1u << PRmloop00) |
                               (1u << PRmloop01) | (1u << PRmloop10);
-// matrix x is one of the six table-carried matrices
-CCJ_HD constexpr bool tab_only(int x) { return (TAB_MASK >> x) & 1u; }
-// its table: 0..2 = F00 F01 F10 (indexed by (i,j)), 3..5 = G00 G01 G10 (indexed by (k,l))
+// table of matrix x: 0..2 = F00 F01 F10 (indexed by (i,j)), 3..5 = G00 G01 G10 (indexed by (k,l))
 CCJ_HD constexpr int tab_index(int x) { return x - PLmloop00; }
 static_assert(tab_index(PLmloop00) == 0 && tab_index(PLmloop10) == 2 && tab_index(PRmloop00) == 3 &&
               tab_index(PRmloop10) == 5, "the six families are consecutive in Mat4");

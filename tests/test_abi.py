@@ -75,18 +75,28 @@ def test_work_model_matches_survey_scale():
     assert 0.9 * 6.29e9 < total < 1.05 * 6.29e9
 
 
-REC_ONLY = (5, 6, 8, 9, 10, 12, 13, 16, 18, 19, 21)  # the record-carried matrices (ccj_engine.h REC_MASK)
+# ccj_engine.h carrier: where the fill keeps each matrix (Mat4 numbers, ccj_energy.h)
+IN_D4 = (0, 1, 2, 3, 4, 7, 17, 20)        # PK PL PR PM PO PfromM PMmloop01 POmloop01: d4 slots
+IN_REC = (5, 6, 8, 9, 16, 18, 19, 21)     # PfromL PfromR PfromMprime PfromO PM/POmloop00, PM/POmloop10: REC_MASK
+IN_TAB = (10, 11, 12, 13, 14, 15)         # PLmloop00/01/10 PRmloop00/01/10: TAB_MASK (ccj_mloop2d.h)
 
 
 def _mslot(x):
-    """ccj_engine.h mslot: the 11 stored matrices in enum order, then the 11 record-carried ones."""
-    below = sum(x > r for r in REC_ONLY)
-    return 11 + below if x in REC_ONLY else x - below
+    """ccj_engine.h mslot: the IN_D4 matrices in enum order, then IN_REC, then IN_TAB."""
+    return (IN_D4 + IN_REC + IN_TAB).index(x)
+
+
+def test_carriers_partition_the_matrices():
+    assert (len(IN_D4), len(IN_REC), len(IN_TAB)) == (8, 8, 6)
+    assert sorted(IN_D4 + IN_REC + IN_TAB) == list(range(22))
+    for cls in (IN_D4, IN_REC, IN_TAB):
+        assert list(cls) == sorted(cls)  # enum order inside a class
+    assert [_mslot(x) for x in (0, 20, 5, 21, 10, 15)] == [0, 7, 8, 15, 16, 21]  # the header's static_asserts
 
 
 def _layout(n, nm4=22):
     """Python restatement of the level-major layout (ccj_engine.h) — brute-force bijection check;
-    nm4 = 11 (d4 without the record-carried matrices) or 22 (mat5, and the host mirror)."""
+    nm4 = 8 (a lean d4: the IN_D4 matrices) or 22 (a full d4, and the host mirror)."""
     off, lv = 0, {}
     for t in range(n):
         m = n - t - 2
@@ -97,7 +107,7 @@ def _layout(n, nm4=22):
 
 
 @pytest.mark.parametrize("n", [5, 9, 17, 24])
-@pytest.mark.parametrize("nm4", [11, 22])
+@pytest.mark.parametrize("nm4", [8, 22])
 def test_level_layout_is_a_bijection(n, nm4):
     lv, total = _layout(n, nm4)
     assert sorted(_mslot(x) for x in range(22)) == list(range(22))

@@ -6,6 +6,10 @@ mirror, the device traceback) is served from the tables.  Everything here is hel
 restatement (OracleFold) with the same sequence and penalties: the default ones and a set with
 negative PSM, PPS, ap, bp and cp (tests/mloop2d_cases.py), under which the six families, the PM / PO
 families and PL / PR are finite, so the shrunk loop records and leader partials carry real values.
+
+Each of the 22 matrices has one carrier (d4, the loop records, the tables: ccj_engine.h carrier), and
+the host mirror get4 reads is put together from all three: one test reads all 22 cell by cell, in
+every kind of context.
 """
 import threading
 
@@ -93,7 +97,7 @@ def _fold_pair(seq, params, dangles, pen_id, **kw):
 
 
 @pytest.mark.parametrize("pen_id", ["def", "neg"])
-@pytest.mark.parametrize("kind", ["default", "mat5", "host_traceback", "sharded2"])
+@pytest.mark.parametrize("kind", ["default", "d4_full", "host_traceback", "sharded2"])
 def test_six_matrices_and_hashes_in_every_kind_of_context(kind, pen_id, monkeypatch):
     seq, params, d = SMALL
     o, want = _oracle(seq, params, d, pen_id)
@@ -109,8 +113,8 @@ def test_six_matrices_and_hashes_in_every_kind_of_context(kind, pen_id, monkeypa
                 wf.close()
             g.close()
         return
-    if kind == "mat5":
-        monkeypatch.setenv("CCJ_MAT5", "1")  # read when the context is created: d4 keeps 22 slots
+    if kind == "d4_full":
+        monkeypatch.setenv("CCJ_D4_FULL", "1")  # read when the context is created: d4 keeps 22 slots
     wf = _wf(seq, params, d, pen_id, host_traceback=(kind == "host_traceback"))
     ref = _wf(seq, params, d, pen_id, host_traceback=(kind != "host_traceback"))  # the other executor
     try:
@@ -134,6 +138,62 @@ def test_negative_set_makes_the_families_finite_at_n32():
     for nm in SIX + ("PMmloop00", "PMmloop10", "POmloop00", "POmloop10", "PL", "PR"):
         x = HASH_NAMES.index(nm)
         assert sum(o.get4(x, *c) < 32767 for c in valid_cells(o.n)) > 1000, nm
+
+
+# ---- n = 32: every cell of all 22 matrices through the host mirror, per kind of context
+_all22 = {}
+
+
+def _oracle_all22():
+    """The restatement's 22 matrices over every valid cell of SMALL under the negative set, read once.
+    The slot order of a level (ccj_engine.h mslot) decides where get4 finds a matrix in the mirror, and
+    a swap of two slots can hide only between matrices that are equal cell for cell: so first, on
+    the restatement alone, every matrix holds many finite values and no two are equal."""
+    if not _all22:
+        seq, params, d = SMALL
+        o, _ = _oracle(seq, params, d, "neg")
+        cells = list(valid_cells(o.n))
+        cols = [[o.get4(x, *c) for c in cells] for x in range(22)]
+        for x in range(22):
+            assert sum(v < 32767 for v in cols[x]) > 1000, HASH_NAMES[x]
+        same = [(HASH_NAMES[x], HASH_NAMES[y]) for x in range(22) for y in range(x + 1, 22) if cols[x] == cols[y]]
+        assert not same, same
+        _all22["cells"], _all22["cols"] = cells, cols
+    return _all22["cells"], _all22["cols"]
+
+
+def _check_all22_cells(wf):
+    cells, cols = _oracle_all22()
+    for x in range(22):
+        diff = [(c, wf.get4(x, *c), v) for c, v in zip(cells, cols[x]) if wf.get4(x, *c) != v]
+        assert not diff, f"{HASH_NAMES[x]}: {len(diff)} cells differ, first (cell, got, oracle) = {diff[0]}"
+
+
+@pytest.mark.parametrize("kind", ["lean", "d4_full", "overlap_d2h", "sharded2"])
+def test_all_22_matrices_cell_by_cell_through_the_host_mirror(kind, monkeypatch):
+    """get4 reads the host mirror (cell_offset_host).  A lean context copies 8 slots per level from
+    d4 and 14 written out from the records and tables; a full one (the switch, a mirror streamed
+    during the fill, each rank of a band-sharded pair) copies d4's 22."""
+    _oracle_all22()
+    seq, params, d = SMALL
+    if kind == "sharded2":
+        g, ranks = _fold_pair(seq, params, d, "neg")
+        try:
+            for wf in ranks:
+                _check_all22_cells(wf)
+        finally:
+            for wf in ranks:
+                wf.close()
+            g.close()
+        return
+    if kind == "d4_full":
+        monkeypatch.setenv("CCJ_D4_FULL", "1")  # read when the context is created
+    wf = _wf(seq, params, d, "neg", overlap_d2h=(kind == "overlap_d2h"))
+    try:
+        wf.fill()
+        _check_all22_cells(wf)
+    finally:
+        wf.close()
 
 
 # ---- n = 57 .. 64: every launch regime of the level chain, and the four leaderless-boundary classes

@@ -1,11 +1,11 @@
 # Level-chain write audit: fill time and rocprofv3 WRITE_SIZE / FETCH_SIZE per
 # level for the default library and timing-only builds that drop one buffer's stores
 # (tools/ablate.sh: NOREC = loop records, NOACC = split-sharing partials, NOCOPY = interior-loop
-# copies, NOMAT5 = the 5 matrices no fill kernel reads back).  Results: gpurun_out/waudit/.
+# copies).  Results: the waudit folder made below.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/waudit
 K="k_level4d|k_iltile|k_iloop|k_ppush"
-for v in - norec noacc nocopy nomat5; do
+for v in - norec noacc nocopy; do
   [ "$v" = "-" ] && lv="" || lv=$v
   echo "== ${v}"
   CCJ_LIB_VARIANT=$lv timeout -k 10 120 python3 tools/level_profile.py 200 > gpurun_out/waudit/time_$v.txt 2>&1 || exit 1
