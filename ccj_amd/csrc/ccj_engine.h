@@ -4,7 +4,7 @@
 //   * 4-D gap matrices: level-major.  A cell (i,j,k,l) has a = j-i, g = k-j (>= 2), b = l-k,
 //     level t = a+b, h = g-2.  Level t holds (t+1) blocks (one per a) of M_t = m_t(m_t+1)/2 cells,
 //     m_t = n-t-2, each block a triangle of rows h = 0..m_t-1 of length m_t-h, i fastest.
-//     Within a level the matrix slots (mslot below: 8 in a lean context, all 22 in a full one) are
+//     Within a level the matrix slots (mslot below: 6 in a lean context, all 22 in a full one) are
 //     stored one after another (SoA), so one level is one contiguous span:
 //     elem(x,t,a,h,i) = LB_t + mslot(x)*C_t + a*M_t + G_t(h) + (i-1),
 //     G_t(h) = h*m_t - h(h-1)/2, C_t = (t+1)*M_t.
@@ -18,47 +18,55 @@
 #include <hip/hip_runtime.h>
 #include "ccj_energy.h"  // Mat4, Penalties
 #include "ccj_mloop2d.h"  // the six table-carried matrices
+#include "ccj_pmpo2d.h"   // the six closed-form matrices
 #include "ccj_params.h"
 
 namespace ccj {
 
 // Every 4-D matrix has exactly one carrier, the place the fill writes it to and every reader takes it
 // from:
-//   IN_D4  (8): its slot of d4.  The level kernel stores it and later levels read it there.
-//   IN_REC (8): the loop records (RA / RK / RL below; rec_get).  A full context (DevTables::full4:
+//   IN_D4  (6): its slot of d4.  The level kernel stores it and later levels read it there.
+//   IN_REC (4): the loop records (RA / RK / RL below; rec_get).  A full context (DevTables::full4:
 //               band-sharded over an exchange, which packs them from d4, or a host mirror streamed
 //               during the fill) stores them in d4 as well and reads them there.
 //   IN_TAB (6): the 2-D tables of the PL / PR multiloop families (ccj_mloop2d.h; tab_get).  The fill
 //               never writes their d4 slots.
-enum Carrier { IN_D4 = 0, IN_REC = 1, IN_TAB = 2 };
-constexpr unsigned REC_MASK = (1u << PfromL) | (1u << PfromR) | (1u << PfromMprime) | (1u << PfromO) | (1u << PMmloop00) |
-                              (1u << PMmloop10) | (1u << POmloop00) | (1u << POmloop10);
-constexpr unsigned D4_MASK = ((1u << NMAT4) - 1u) & ~(REC_MASK | TAB_MASK);
-static_assert((REC_MASK & TAB_MASK) == 0, "one carrier per matrix");
+//   IN_CF  (6): the PM / PO multiloop families, evaluated in closed form from nine 2-D tables
+//               (ccj_pmpo2d.h; cf_get).  The fill never computes them for a cell's own sake and
+//               never writes their d4 slots.
+enum Carrier { IN_D4 = 0, IN_REC = 1, IN_TAB = 2, IN_CF = 3 };
+constexpr unsigned REC_MASK = (1u << PfromL) | (1u << PfromR) | (1u << PfromMprime) | (1u << PfromO);
+constexpr unsigned D4_MASK = ((1u << NMAT4) - 1u) & ~(REC_MASK | TAB_MASK | CF_MASK);
+static_assert((REC_MASK & TAB_MASK) == 0 && (REC_MASK & CF_MASK) == 0 && (TAB_MASK & CF_MASK) == 0, "one carrier per matrix");
 __host__ __device__ constexpr Carrier carrier(int x) {
-    return (TAB_MASK >> x) & 1u ? IN_TAB : (REC_MASK >> x) & 1u ? IN_REC : IN_D4;
+    return (TAB_MASK >> x) & 1u ? IN_TAB : (CF_MASK >> x) & 1u ? IN_CF : (REC_MASK >> x) & 1u ? IN_REC : IN_D4;
 }
-constexpr int NMAT_D4 = __builtin_popcount(D4_MASK), NMAT_REC = __builtin_popcount(REC_MASK), NMAT_TAB = __builtin_popcount(TAB_MASK);
+constexpr int NMAT_D4 = __builtin_popcount(D4_MASK), NMAT_REC = __builtin_popcount(REC_MASK), NMAT_TAB = __builtin_popcount(TAB_MASK),
+              NMAT_CF = __builtin_popcount(CF_MASK);
 // Storage slot of matrix x inside a level of d4 and of the host mirror: the IN_D4 matrices in enum
-// order, then IN_REC, then IN_TAB.  d4 holds slots [0, NMAT_D4) per level, or all 22 in a full
-// context; the host mirror always holds 22 (ccjk_expand writes out what d4 lacks).  Matrix-major
-// "level element" indices of the exchange API (x*C + a*M + c) are by matrix, not by slot.
+// order, then IN_REC, then IN_TAB, then IN_CF (the two classes the fill never writes come last, so one
+// ccjk_expand from slot NMAT_D4 + NMAT_REC covers both).  d4 holds slots [0, NMAT_D4) per level, or all
+// 22 in a full context; the host mirror always holds 22 (ccjk_expand writes out what d4 lacks).
+// Matrix-major "level element" indices of the exchange API (x*C + a*M + c) are by matrix, not by slot.
 __host__ __device__ constexpr int mslot(int x) {
     const Carrier c = carrier(x);
-    const unsigned cls = c == IN_D4 ? D4_MASK : c == IN_REC ? REC_MASK : TAB_MASK;
-    const int first = c == IN_D4 ? 0 : c == IN_REC ? NMAT_D4 : NMAT_D4 + NMAT_REC;
+    const unsigned cls = c == IN_D4 ? D4_MASK : c == IN_REC ? REC_MASK : c == IN_TAB ? TAB_MASK : CF_MASK;
+    const int first = c == IN_D4 ? 0 : c == IN_REC ? NMAT_D4 : c == IN_TAB ? NMAT_D4 + NMAT_REC : NMAT_D4 + NMAT_REC + NMAT_TAB;
     return first + __builtin_popcount(cls & ((1u << x) - 1u));
 }
-static_assert(NMAT_D4 == 8 && NMAT_REC == 8 && NMAT_TAB == 6 && NMAT_D4 + NMAT_REC + NMAT_TAB == NMAT4, "the partition");
-static_assert(carrier(PK) == IN_D4 && mslot(PK) == 0 && mslot(PO) == 4 && mslot(PfromM) == 5 && carrier(POmloop01) == IN_D4 &&
-                  mslot(POmloop01) == NMAT_D4 - 1,
+static_assert(NMAT_D4 == 6 && NMAT_REC == 4 && NMAT_TAB == 6 && NMAT_CF == 6 && NMAT_D4 + NMAT_REC + NMAT_TAB + NMAT_CF == NMAT4,
+              "the partition");
+static_assert(carrier(PK) == IN_D4 && mslot(PK) == 0 && mslot(PO) == 4 && carrier(PfromM) == IN_D4 && mslot(PfromM) == NMAT_D4 - 1,
               "d4 slots");
-static_assert(carrier(PfromL) == IN_REC && mslot(PfromL) == NMAT_D4 && carrier(POmloop10) == IN_REC &&
-                  mslot(POmloop10) == NMAT_D4 + NMAT_REC - 1,
+static_assert(carrier(PfromL) == IN_REC && mslot(PfromL) == NMAT_D4 && carrier(PfromO) == IN_REC &&
+                  mslot(PfromO) == NMAT_D4 + NMAT_REC - 1,
               "record-carried slots");
 static_assert(carrier(PLmloop00) == IN_TAB && mslot(PLmloop00) == NMAT_D4 + NMAT_REC && carrier(PRmloop10) == IN_TAB &&
-                  mslot(PRmloop10) == NMAT4 - 1,
+                  mslot(PRmloop10) == NMAT_D4 + NMAT_REC + NMAT_TAB - 1,
               "table-carried slots");
+static_assert(carrier(PMmloop00) == IN_CF && mslot(PMmloop00) == NMAT4 - NMAT_CF && carrier(POmloop10) == IN_CF &&
+                  mslot(POmloop10) == NMAT4 - 1,
+              "closed-form slots");
 
 constexpr int IE_U = 29;  // u1,u2 in [0,28] for pseudoknot interior loops (pseudo_loop.cc:694-806)
 #ifndef CCJ_ILB
@@ -81,26 +89,26 @@ struct LevelDesc {
 
 struct LvlDev {     // per-level descriptor read by the level kernel (one s_load_dwordx8)
     long long lb;  // element offset of level t in the 4-D storage
-    long long lr;  // record offset of level t in the AoS loop records (3 record types x C)
+    long long lr;  // record offset of level t in each of the three loop-record arrays (cells of the levels below)
     int C;         // cells per matrix in level t = (t+1)*M
     int M;         // cells per a-block = m(m+1)/2, m = n-t-2
     int pad[2];
 };
 
 // AoS loop records: the operands the fused split-point loops of k_level4d read at
-// one neighbour cell, int16 fields packed in one record, so each neighbour costs one dwordx3 (dwordx2)
-// load instead of 4-6 int16 loads.  Three record types per level, each indexed like a matrix
-// (a*M + G(h) + i-1): RA and RL (12 bytes) in T.rec, level t at ld[t].lr (RA: C records, then RL),
-// RK (8 bytes) in T.rk at ld[t].lr / 2:
-//   RA (a-loop, both sides): PMmloop00 POmloop00 | PfromL PfromO | PfromMprime PK
-//   RK (b-loop, k side):     PMmloop00 PfromR | min(PL,PR) PK
-//   RL (b-loop, l side):     PMmloop00 POmloop00 | PMmloop10 POmloop10 | PfromR PfromO
-// Values are the stored (clamped) int16 matrix values.  (The PL / PR multiloop families are not in
-// the records: they are 2-D tables, ccj_mloop2d.h.)
-enum RecType { RA = 0, RL = 1, NREC = 2 };  // 12-byte record types in T.rec (RK lives in T.rk)
-typedef uint3 rec_t;  // RA, RL
-typedef uint2 rk_t;   // RK
-static_assert(sizeof(rec_t) == 12 && sizeof(rk_t) == 8, "record sizes");
+// one neighbour cell, int16 fields packed in one record, so each neighbour costs one dwordx2 (dword)
+// load instead of 2-4 int16 loads.  Three record types, each its own array indexed like a matrix
+// (ld[t].lr + a*M + G(h) + i-1): 20 bytes per cell
+//   RA (a-loop, both sides; T.rec, 8 B): PfromL PfromO | PfromMprime PK
+//   RK (b-loop, k side;     T.rk,  8 B): PfromR min(PL,PR) | PK -
+//   RL (b-loop, l side;     T.rl,  4 B): PfromR PfromO
+// Values are the stored (clamped) int16 matrix values.  (The multiloop families are not in the records:
+// PL / PR are 2-D tables, ccj_mloop2d.h; PM / PO closed forms of 2-D tables, ccj_pmpo2d.h.)
+typedef uint2 rec_t;     // RA
+typedef uint2 rk_t;      // RK
+typedef unsigned rl_t;   // RL
+static_assert(sizeof(rec_t) == 8 && sizeof(rk_t) == 8 && sizeof(rl_t) == 4, "record sizes");
+constexpr int REC_BYTES = (int)(sizeof(rec_t) + sizeof(rk_t) + sizeof(rl_t));  // per cell
 
 // Split-point sharing (k_level4d).  The cells of one gap column — same (j,k,l)
 // for the i-side split, (i,k,l) j-side, (i,j,l) k-side, (i,j,k) l-side — sit on consecutive levels
@@ -109,14 +117,14 @@ static_assert(sizeof(rec_t) == 12 && sizeof(rk_t) == 8, "record sizes");
 // range once and also reduces it for the next SHARE_R-1 cells of each of its columns; those
 // followers scan only the split points the leader did not see and take the rest from a partial
 // record.  Partial records live in a ring of SHARE_R level slots (the level t' cells' records are
-// written at levels t'-SHARE_R+1 .. t'-1 and read at t'), SHARE_NACC 16-byte slots per cell, of which
-// a record uses its first 12 / 8 / 8 / 16 bytes:
-//   AI (i side, 12 B): PMmloop10 POmloop00 | POmloop10 PfromL | PfromO -
-//   AJ (j side,  8 B): PMmloop00 PfromL | PfromMprime PK
-//   AK (k side,  8 B): PMmloop00 PfromR | PfromM'' PK
-//   AL (l side, 16 B): PMmloop01 POmloop00 | POmloop01 PMmloop10 | POmloop10 PfromR | PfromO -
+// written at levels t'-SHARE_R+1 .. t'-1 and read at t'), SHARE_NACC 8-byte slots per cell, of which
+// a record uses its first 4 / 8 / 8 / 4 bytes:
+//   AI (i side, 4 B): PfromL PfromO
+//   AJ (j side, 8 B): PfromL PfromMprime | PK -
+//   AK (k side, 8 B): PfromR PfromM'' | PK -
+//   AL (l side, 4 B): PfromR PfromO
 // Values are min-clamped at 32767 like a store (clamp commutes with min).  The leader's W(i-r, .) / W(., j+r) operands are read
-// from the span-major WBW pairs (span s-1+r, coalesced along the lanes).
+// from the span-major WP plane (span s-1+r, coalesced along the lanes).
 #ifndef CCJ_SHARE_R
 #define CCJ_SHARE_R 4
 #endif
@@ -228,19 +236,23 @@ struct DevTables {
     const int16_t *est;            // [w][p] e_stP, saturated at 32767
     int16_t *ie;                   // [w][p] e_intP of the u1 = u2 = 0 interior loop (k_precompute_ie), 32767 where skipped
     int *V; int8_t *Vt; int *WM, *WMv, *WMp, *P, *WBP, *WPP, *WB, *WP;  // [w][p]
-    int2 *WBW;                     // [w][p] (WBP, WP): the two 2-D operands of a k_level4d split step, one load
+    int2 *WBW;                     // [w][p] (WBP, WP) in one word pair (k_diag2d's table workgroups read .x)
     unsigned long long *Pk;        // [w][p] (P + 2^31) << 32 | first (j,d,k) split of the minimum (k_pterm)
     const LevelDesc *lv;           // per level t
     int16_t *d4;                   // 4-D storage base
     const long long *lb;           // element offset of level t in d4
     const LvlDev *ld;             // per-level descriptors
-    rec_t *rec;                    // AoS loop records RA, RL: level t at ld[t].lr
-    long long nrec;                // records allocated (debug bounds checks)
-    rk_t *rk;                      // RK records: level t at ld[t].lr / 2 (nrec / 2 of them)
+    rec_t *rec;                    // RA loop records: level t at ld[t].lr
+    long long nrec;                // records allocated per array (debug bounds checks)
+    rk_t *rk;                      // RK records, indexed like rec
+    rl_t *rl;                      // RL records, indexed like rec
     // the PL / PR multiloop families (ccj_mloop2d.h): six int16 tables [w][p], row stride rs, one
     // after another (tab_index) tabN elements apart; span w is written by k_diag2d(w)
     int16_t *tab;
     long long tabN;
+    // the PM / PO multiloop families (ccj_pmpo2d.h): NCF int32 tables [w][p] (CfTab), tabN elements
+    // apart; span w is written by k_diag2d(w)
+    int *cf;
     // interior-loop copies of PL / PR / PM, laid out so that the lanes of one k_iloop wave share
     // the loop's closing pair:
     //   PLx(t,a,h,i) = lbx + a*M + G(i-1) + h               (h fastest: fixed (i,j), lanes k)
@@ -270,7 +282,7 @@ struct DevTables {
     const int16_t *lord;
     const int *lord_off;
     const int *lord_off_h;
-    uint4 *acc;
+    uint2 *acc;
     long long accC;
 };
 
@@ -278,19 +290,12 @@ __device__ __forceinline__ int rlo16(unsigned w) { return (int)(int16_t)(w & 0xf
 __device__ __forceinline__ int rhi16(unsigned w) { return (int)(int16_t)(w >> 16); }
 // an IN_REC matrix from the records of the cell at in-level offset cell (a*M + G(h) + i-1)
 __device__ __forceinline__ int rec_get(const DevTables &T, int x, const LvlDev &L, long long cell) {
-    const rec_t *rp = T.rec + L.lr;
-    if (x == PfromR) return rhi16(T.rk[(L.lr >> 1) + cell].x);  // RK: Mm00|fR, PLR|K
-    if (x == PMmloop10 || x == POmloop10) {  // RL: Mm00|Om00, Mm10|Om10, fR|fO
-        const rec_t r = rp[(long long)L.C + cell];
-        return x == PMmloop10 ? rlo16(r.y) : rhi16(r.y);
-    }
-    const rec_t r = rp[cell];  // RA: Mm00|Om00, fL|fO, fMp|K
+    if (x == PfromR) return rlo16(T.rl[L.lr + cell]);  // RL: fR|fO
+    const rec_t r = T.rec[L.lr + cell];  // RA: fL|fO, fMp|K
     switch (x) {
-        case PMmloop00: return rlo16(r.x);
-        case POmloop00: return rhi16(r.x);
-        case PfromL: return rlo16(r.y);
-        case PfromO: return rhi16(r.y);
-        default: return rlo16(r.z);  // PfromMprime
+        case PfromL: return rlo16(r.x);
+        case PfromO: return rhi16(r.x);
+        default: return rlo16(r.y);  // PfromMprime
     }
 }
 // an IN_TAB matrix at cell (i,j,k,l)
@@ -300,10 +305,22 @@ __device__ __forceinline__ int tab_get(const DevTables &T, int x, int i, int j, 
     return (int)T.tab[(long long)ti * T.tabN + w * T.rs + p];
 }
 
+// an IN_CF matrix at cell (i,j,k,l): the closed form over the nine tables
+struct CfTabs {
+    const int *cf;
+    long long N;
+    int rs;
+    __device__ __forceinline__ int operator()(int f, int p, int q) const { return cf[(long long)f * N + (q - p) * rs + p]; }
+};
+__device__ __forceinline__ int cf_get(const DevTables &T, int x, int i, int j, int k, int l) {
+    return pmpo2d_eval(x, T.pen.bp, T.pen.cp, CfTabs{T.cf, T.tabN, T.rs}, i, j, k, l);
+}
+
 // The one read of matrix x at cell (i,j,k,l) of level L outside the fill's own hot loops (hashes,
 // traceback, host mirror): by carrier; cell = a*M + G(h) + i-1.
 __device__ __forceinline__ int mat4_get(const DevTables &T, int x, const LvlDev &L, long long cell, int i, int j, int k, int l) {
     if (carrier(x) == IN_TAB) return tab_get(T, x, i, j, k, l);
+    if (carrier(x) == IN_CF) return cf_get(T, x, i, j, k, l);
     if (carrier(x) == IN_REC && !T.full4) return rec_get(T, x, L, cell);
     return (int)T.d4[L.lb + (long long)mslot(x) * L.C + cell];
 }

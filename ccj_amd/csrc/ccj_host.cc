@@ -137,10 +137,12 @@ struct ccj_ctx {
     LvlDev *d_ld = nullptr;
     int16_t *d4x = nullptr, *pmx = nullptr;  // interior-loop copies of PL/PR and PM (IT_PAD into the allocations)
     int16_t *d4x_alloc = nullptr, *pmx_alloc = nullptr;
-    rec_t *d_rec = nullptr;                  // AoS loop records RA, RL (12 bytes)
-    rk_t *d_rk = nullptr;                    // AoS loop records RK (8 bytes)
+    rec_t *d_rec = nullptr;                  // loop records RA (8 bytes)
+    rk_t *d_rk = nullptr;                    // loop records RK (8 bytes)
+    rl_t *d_rl = nullptr;                    // loop records RL (4 bytes)
+    int *d_cf = nullptr;                     // the nine PM / PO closed-form tables [w][p] (ccj_pmpo2d.h)
     int16_t *d_tab = nullptr;                // the six PL / PR multiloop tables [w][p] (ccj_mloop2d.h)
-    uint4 *d_acc = nullptr;                  // partial-record ring (split-point sharing)
+    uint2 *d_acc = nullptr;                  // partial-record ring (split-point sharing)
     int16_t *d_lord = nullptr;               // long-scan a-blocks per sharing level, longest first
     int *d_lord_off = nullptr;
     std::vector<int> lord_off;
@@ -853,12 +855,12 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     const size_t ie_elems = (size_t)(n + 1) * c->rs;  // the u1 = u2 = 0 plane (k_build_il evaluates the rest)
     if (c->total4 > 0 && hipMalloc(&c->d4, (size_t)c->total4 * sizeof(int16_t)) != hipSuccess)
         return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for 4-D matrices failed", c->total4 * 2e-9);
-    // AoS loop records: NREC 12-byte records and one 8-byte RK record per cell (ccj_engine.h)
-    c->nrec = c->ncell * NREC;
+    // loop records: one RA (8 bytes), RK (8) and RL (4) record per cell, each its own array (ccj_engine.h)
+    c->nrec = c->ncell;
     if (c->nrec > 0 && (hipMalloc(&c->d_rec, (size_t)c->nrec * sizeof(rec_t)) != hipSuccess ||
-                        hipMalloc(&c->d_rk, (size_t)c->ncell * sizeof(rk_t)) != hipSuccess))
-        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for loop records failed",
-                       c->nrec * 12e-9 + c->ncell * 8e-9);
+                        hipMalloc(&c->d_rk, (size_t)c->nrec * sizeof(rk_t)) != hipSuccess ||
+                        hipMalloc(&c->d_rl, (size_t)c->nrec * sizeof(rl_t)) != hipSuccess))
+        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for loop records failed", c->nrec * (REC_BYTES * 1e-9));
     // split-point sharing: the level range it covers (every level of it runs unsplit, so each leader
     // and its followers run one cell per lane) and the partial-record ring
     int g_lo = 0, g_hi = 0;
@@ -896,9 +898,9 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
         HIPCHK(cp, hipMemcpy(c->d_lord_off, c->lord_off.data(), c->lord_off.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     if (g_hi > g_lo) {
-        if (hipMalloc(&c->d_acc, (size_t)SHARE_SLOTS * SHARE_NACC * accC * sizeof(uint4)) != hipSuccess)
+        if (hipMalloc(&c->d_acc, (size_t)SHARE_SLOTS * SHARE_NACC * accC * sizeof(uint2)) != hipSuccess)
             return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for split-sharing records failed",
-                           SHARE_SLOTS * SHARE_NACC * accC * 16e-9);
+                           SHARE_SLOTS * SHARE_NACC * accC * 8e-9);
     }
     HIPCHK(cp, hipMalloc(&c->d_ie, ie_elems * sizeof(int16_t)));
     HIPCHK(cp, hipMalloc(&c->d_est, plane * sizeof(int16_t)));
@@ -964,6 +966,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     HIPCHK(cp, hipMalloc(&c->d2i, A2_N * plane * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_wbw, plane * sizeof(int2)));
     HIPCHK(cp, hipMalloc(&c->d_tab, 6 * plane * sizeof(int16_t)));  // k_init2d resets them with every fill
+    HIPCHK(cp, hipMalloc(&c->d_cf, NCF * plane * sizeof(int)));     // and these
     HIPCHK(cp, hipMalloc(&c->d_pk, plane * sizeof(unsigned long long)));
     HIPCHK(cp, hipMalloc(&c->d_W, (n + 1) * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_wterm, plane * sizeof(int)));
@@ -998,7 +1001,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
         long long lr = 0;
         for (size_t t = 0; t < ld.size(); ++t) {
             ld[t] = LvlDev{c->lv_off[t], lr, c->lv_host[t].C, c->lv_host[t].M, {0, 0}};
-            lr += (long long)NREC * c->lv_host[t].C;
+            lr += (long long)c->lv_host[t].C;
         }
         HIPCHK(cp, hipMemcpy(c->d_ld, ld.data(), ld.size() * sizeof(LvlDev), hipMemcpyHostToDevice));
     }
@@ -1040,6 +1043,8 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.d4x = c->d4x;
     T.rec = c->d_rec;
     T.rk = c->d_rk;
+    T.rl = c->d_rl;
+    T.cf = c->d_cf;
     T.tab = c->d_tab;
     T.tabN = (long long)plane;
     T.nrec = c->nrec;
@@ -1143,8 +1148,9 @@ static int pterm_launch(const ccj_ctx *c, int lev, hipStream_t s) {
     return 0;
 }
 
-// A full context's d4 has the host mirror's layout except that the fill leaves the IN_TAB slots of
-// every level unwritten: write level t's from the tables, in front of a copy to the mirror.
+// A full context's d4 has the host mirror's layout except that the fill leaves the IN_TAB and IN_CF
+// slots (the last twelve) of every level unwritten: write level t's from the tables, in front of a
+// copy to the mirror.
 static int expand_tab_slots(const ccj_ctx *c, int t, hipStream_t s) {
     constexpr int first = NMAT_D4 + NMAT_REC;
     return ccjk_expand(&c->T, t, first, c->d4 + c->lv_off[t] + (size_t)first * c->lv_host[t].C, s);
@@ -2144,6 +2150,8 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
     hipFree(c->d_ioff);
     hipFree(c->d_rec);
     hipFree(c->d_rk);
+    hipFree(c->d_rl);
+    hipFree(c->d_cf);
     hipFree(c->d_acc);
     hipFree(c->d_wterm);
     hipFree(c->d_lord);

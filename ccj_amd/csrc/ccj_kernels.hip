@@ -3,8 +3,9 @@
 // Schedule: for sigma = 0..n-1
 //     k_diag2d(sigma)   : every 2-D interval value of span sigma (V, P, WBP, WPP, WMv, WMp, WM), and
 //                         span sigma of the PL / PR multiloop tables (six gap matrices that depend
-//                         on two indices only, ccj_mloop2d.h)
-//     k_level4d(t=sigma): every 4-D cell of level t = (j-i)+(l-k), the other 16 gap matrices
+//                         on two indices only, ccj_mloop2d.h) and of the PM / PO multiloop families'
+//                         closed-form tables (six more, const + f(i,j) + g(k,l), ccj_pmpo2d.h)
+//     k_level4d(t=sigma): every 4-D cell of level t = (j-i)+(l-k), the other 10 gap matrices
 // Level t reads only 4-D levels < t and 2-D spans <= t-1; span sigma reads 4-D levels <= sigma-3.
 // Within a cell the 22 recurrences run in the reference's order (pseudo_loop.cc:85-127), so the
 // same-cell reads (PfromL/PfromR/PfromO/PK read PL/PR/PM/PO of the cell) see the finished
@@ -195,6 +196,9 @@ __global__ void k_init2d(DevTables T, int total) {
         // the PL / PR multiloop tables (ccj_mloop2d.h): never set = 32767, like a Matrix4D cell
 #pragma unroll
         for (int f = 0; f < 6; ++f) T.tab[f * T.tabN + x] = (int16_t)INTERN_INF;
+        // the PM / PO closed-form tables (ccj_pmpo2d.h): every span is rewritten by k_diag2d
+#pragma unroll
+        for (int f = 0; f < NCF; ++f) T.cf[f * T.tabN + x] = INF;
     }
 }
 
@@ -265,6 +269,38 @@ __device__ __forceinline__ void diag2d_tables(const DevTables &T, int sigma, int
     for (int f = 0; f < 6; ++f) T.tab[f * T.tabN + cell] = (int16_t)mloop2d_store(v[f]);
 }
 
+// Span sigma of the nine closed-form tables of the PM / PO multiloop families (ccj_pmpo2d.h): further
+// work items of the same launch, one wave per interval, lanes over the split steps.  Like the PL / PR
+// tables they read WBP of spans <= sigma-1 and their own spans < sigma only.
+__device__ __forceinline__ void diag2d_cf(const DevTables &T, int sigma, int item) {
+    const int n = T.n, rs = T.rs, w = sigma;
+    const int p = 1 + item, q = p + w;
+    if (q > n) return;  // whole wave
+    const int lane = threadIdx.x & 63;
+    const int cp = T.pen.cp;
+    const long long N = T.tabN;
+    const int *__restrict__ cf = T.cf;
+    Pmpo2dAcc R = pmpo2d_begin();
+    for (int s = 1 + lane; s <= w; s += 64) {
+#ifdef CCJ_DEBUG_BOUNDS
+        if (p + s > n || q - s + 1 < 1 || w - s < 0) atomicOr(T.err, 512);
+#endif
+        const int head = T.WBW[(s - 1) * rs + p].x, tail = T.WBW[(s - 1) * rs + q - s + 1].x;
+        const int o = (w - s) * rs + p;  // span w-s: (p, q-s) at o, (p+s, q) at o+s
+        pmpo2d_step(R, s, w, cp, head, tail, cf[CF_A * N + o], cf[CF_AO * N + o], cf[CF_Z * N + o], cf[CF_ZO * N + o],
+                    cf[CF_CL * N + o], cf[CF_A * N + o + s], cf[CF_AO * N + o + s]);
+    }
+    R.a = wave_min(R.a); R.ao = wave_min(R.ao); R.u = wave_min(R.u); R.uo = wave_min(R.uo); R.x = wave_min(R.x);
+    R.xo = wave_min(R.xo); R.z = wave_min(R.z); R.zo = wave_min(R.zo); R.cl = wave_min(R.cl);
+    if (lane != 0) return;
+    const int o1 = (w - 1) * rs + p;  // span w-1: (p, q-1) at o1, (p+1, q) at o1+1
+    int out[NCF];
+    pmpo2d_end(R, w, cp, w >= 1 ? cf[CF_UP * N + o1] : 0, w >= 1 ? cf[CF_Y * N + o1 + 1] : 0, out);
+    const int cell = w * rs + p;
+#pragma unroll
+    for (int f = 0; f < NCF; ++f) T.cf[f * N + cell] = out[f];
+}
+
 __global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, int rank, int nb) {
 #ifdef CCJ_DEBUG_BOUNDS
     g_dbg_err = T.err;
@@ -272,7 +308,10 @@ __global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, i
     TL_STAMP(sigma == L_ - 1 || sigma == L_ ? 7 : -1);
     TL_META(sigma);
     if ((int)blockIdx.x >= nb) {  // whole workgroup: no barrier below is reached
-        diag2d_tables(T, sigma, ((int)blockIdx.x - nb) * 4 + (int)(threadIdx.x >> 6));
+        // items [0, nint): the PL / PR tables; [nint, 2 nint): the PM / PO closed-form tables
+        const int item = ((int)blockIdx.x - nb) * 4 + (int)(threadIdx.x >> 6), nint = T.n - sigma;
+        if (item < nint) diag2d_tables(T, sigma, item);
+        else diag2d_cf(T, sigma, item - nint);
         return;
     }
     __shared__ int red[4];
@@ -1174,28 +1213,25 @@ __device__ __forceinline__ int lo16(unsigned w) { return (int)(int16_t)(w & 0xff
 __device__ __forceinline__ int hi16(unsigned w) { return (int)w >> 16; }
 
 // ints per lane a leader's split wave hands to part 0: the followers' slices r = 1..R-1 of one side
-constexpr int LA_I = 5, LA_J = 4, LB_K = 4, LB_L = 7;  // fields per follower slice: i, j, k, l side
+constexpr int LA_I = 2, LA_J = 3, LB_K = 3, LB_L = 2;  // fields per follower slice: i, j, k, l side
 constexpr int LEAD_RED = (LA_I + LA_J > LB_K + LB_L ? LA_I + LA_J : LB_K + LB_L) * SHARE_R;
 // ints per lane a split wave of the plain loops hands to part 0 (the accumulators of both loops)
-constexpr int SPLIT_RED = 16;
+constexpr int SPLIT_RED = 10;
 
-// split-point sharing (ccj_engine.h): the SHARE_R W values of one split step, one per follower
-typedef int wv_t __attribute__((ext_vector_type(SHARE_R)));
-// partial record: up to 7 int16 fields (min-clamped like a store), slot 7 = 32767
-__device__ __forceinline__ uint4 pack_acc(const int *f, int nf) {
-    int c[8];
+// partial record: up to 3 int16 fields (min-clamped like a store), the others 32767
+__device__ __forceinline__ uint2 pack_acc(const int *f, int nf) {
+    int c[4];
 #pragma unroll
-    for (int x = 0; x < 8; ++x) c[x] = x < nf ? clamp_store(f[x]) : INTERN_INF;
-    return make_uint4(pk16(c[0], c[1]), pk16(c[2], c[3]), pk16(c[4], c[5]), pk16(c[6], c[7]));
+    for (int x = 0; x < 4; ++x) c[x] = x < nf ? clamp_store(f[x]) : INTERN_INF;
+    return make_uint2(pk16(c[0], c[1]), pk16(c[2], c[3]));
 }
 
-// the three records of one cell (values as stored, i.e. already clamped)
-__device__ __forceinline__ void write_records(const DevTables &T, long long lr, int C, unsigned cell, int Mm00, int Om00,
-                                              int fL, int fO, int fMp, int K, int fR, int PLR, int Mm10, int Om10) {
-    rec_t *rp = T.rec + lr;
-    rp[cell] = make_uint3(pk16(Mm00, Om00), pk16(fL, fO), pk16(fMp, K));                // RA
-    T.rk[(lr >> 1) + cell] = make_uint2(pk16(Mm00, fR), pk16(PLR, K));                  // RK
-    rp[(unsigned)C + cell] = make_uint3(pk16(Mm00, Om00), pk16(Mm10, Om10), pk16(fR, fO));  // RL
+// the three records of one cell (values as stored, i.e. already clamped); cell = ld[t].lr + in-level offset
+__device__ __forceinline__ void write_records(const DevTables &T, long long cell, int fL, int fO, int fMp, int K, int fR,
+                                              int PLR) {
+    T.rec[cell] = make_uint2(pk16(fL, fO), pk16(fMp, K));                   // RA
+    T.rk[cell] = make_uint2(pk16(fR, PLR), pk16(K, INTERN_INF));            // RK
+    T.rl[cell] = pk16(fR, fO);                                              // RL
 }
 
 
@@ -1306,16 +1342,11 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 
     const Penalties pe = T.pen;
     const int bp = pe.bp, cp = pe.cp, PB = pe.PB, apbp2 = pe.ap + 2 * pe.bp;
-    const int *__restrict__ WB = T.WB;
+    // the one 2-D operand of a split step: WP (get_WP, pseudo_loop.cc:655-661, as k_diag2d stores it)
     const int *__restrict__ WP = T.WP;
-    const int *__restrict__ WBPr = T.WBP;
-    const int2 *__restrict__ WBW = T.WBW;
     const LvlDev *__restrict__ LD = T.ld;
     const int16_t *__restrict__ D4 = T.d4;
 #define LDX(lp, L, x, U, ln) ((int)(lp)[(unsigned)(mslot(x) * (L).C + (U)) + (ln)])
-    // WB of an interval of `len` bases from its WBP, as k_diag2d stores it (get_WB,
-    // pseudo_loop.cc:647-653: min(cp*len, WBP)): one load fewer per split side
-#define WBD(wbp, len) imin(cp * (len), (wbp))
 #ifdef CCJ_DEBUG_BOUNDS
 #define CHK(dt, ap_, dh, di) \
     if ((dt) < 1 || (dt) > t || (ap_) < 0 || (ap_) > t - (dt) || h + (dh) >= m + (dt) || i + (di) < 1 || \
@@ -1323,7 +1354,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 #define CHKR(idx) \
     if ((long long)(idx) < 0 || (long long)(idx) >= T.nrec) atomicOr(T.err, 8)
 #define CHKK(idx) \
-    if ((long long)(idx) < 0 || (long long)(idx) >= T.nrec / 2) atomicOr(T.err, 8)
+    if ((long long)(idx) < 0 || (long long)(idx) >= T.nrec) atomicOr(T.err, 8)
 #define CHKA(idx) \
     if (!T.acc || (long long)(idx) >= T.accC) atomicOr(T.err, 256)
 #else
@@ -1357,17 +1388,14 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     const int b_stop = brole == 2 ? rb : b;
 
     // ---- fused a-loop: split point d inside [i, j] ----
-    const int seed = INTERN_INF + bp;  // A-Q3 seeds
-    int pMm00 = seed, pMm10 = INF;
-    int pOm00 = seed, pOm10 = INF;
+    // (the PM / PO multiloop families' split terms, :544-644, are not here: closed forms, ccj_pmpo2d.h)
     int fL1 = INF, fL2 = INF, fM = INF, fO1 = INF, pK1 = INF;
-    struct AV { int2 w2i, w2j; rec_t wi, wj; int s; };  // raw loads of one split step
+    struct AV { int wpi, wpj; rec_t wi, wj; };  // raw loads of one split step
     auto load_a = [&](int s) {
         AV v;
-        v.s = s;
         const int r2 = (s - 1) * rs, jl = j - s + 1;
-        v.w2i = WBW[r2 + i];  // (WBP, WP) of (i, i+s-1)
-        v.w2j = WBW[r2 + jl];  // (WBP, WP) of (j-s+1, j)
+        v.wpi = WP[r2 + i];   // WP(i, i+s-1)
+        v.wpj = WP[r2 + jl];  // WP(j-s+1, j)
         CHK(s, a - s, 0, s);
         CHK(s, a - s, s, 0);
 #ifdef CCJ_ABLATE_LOCAL
@@ -1379,7 +1407,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Ui = (a - s) * L.M + s;                          // X(d,j,k,l), d = i+s: lane L0 + h*s
         const int Uj = (a - s) * L.M + s * m + ((s * (s + 1)) >> 1);  // X(i,d,k,l), d = j-s: lane L0
         const unsigned lh = L0 + uh * (unsigned)s;
-        // one RA record per side (ccj_engine.h): x = Mm00|Om00, y = fL|fO, z = fMp|K
+        // one RA record per side (ccj_engine.h): x = fL|fO, y = fMp|K
         const rec_t *rp = T.rec + L.lr;
         CHKR(L.lr + (unsigned)Ui + lh);
         CHKR(L.lr + (unsigned)Uj + L0);
@@ -1389,15 +1417,10 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     };
     // (the PL multiloop family's five terms, :449-486, are not here: 2-D tables, ccj_mloop2d.h)
     auto step_a = [&](const AV &v, int mask) {
-        const int wbp_i = v.w2i.x, wp_i = v.w2i.y, wbp_j = v.w2j.x, wp_j = v.w2j.y;
-        const int wb_i = WBD(wbp_i, v.s), wb_j = WBD(wbp_j, v.s);
-        const int Mm00i = lo16(v.wi.x), Om00i = hi16(v.wi.x), fLi = lo16(v.wi.y), fOi = hi16(v.wi.y);
-        const int Mm00j = lo16(v.wj.x), fLj = lo16(v.wj.y);
-        const int fMpj = lo16(v.wj.z), Kj = hi16(v.wj.z);
-        pMm00 = imin(pMm00, Mm00j + wb_j);                      // :548-551
-        pMm10 = imin(pMm10, wbp_i + Mm00i);                     // :581-584
-        pOm00 = imin(pOm00, wb_i + Om00i);                      // :599-602
-        pOm10 = imin(pOm10, wbp_i + Om00i);                     // :632-635
+        const int wp_i = v.wpi, wp_j = v.wpj;
+        const int fLi = lo16(v.wi.x), fOi = hi16(v.wi.x);
+        const int fLj = lo16(v.wj.x);
+        const int fMpj = lo16(v.wj.y), Kj = hi16(v.wj.y);
         fL1 = imin(fL1, fLi + wp_i + mask);        // PfromL(d,j,k,l) + WP(i,d-1)      :357-359
         fO1 = imin(fO1, fOi + wp_i + mask);        // PfromO(d,j,k,l) + WP(i,d-1)      :425-427
         fL2 = imin(fL2, fLj + wp_j + mask);        // PfromL(i,d,k,l) + WP(d+1,j)      :360-361
@@ -1417,10 +1440,9 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 #pragma unroll
             for (int f = 0; f < LA_J; ++f) AJ_[r][f] = INF;
         }
-        struct LA { rec_t wi, wj; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
+        struct LA { rec_t wi, wj; int q[SHARE_R], p[SHARE_R]; };  // raw loads of one split step
         auto ld = [&](int s) {
             LA v;
-            v.s = s;
             const LvlDev L = LD[t - s];
             const int Ui = (a - s) * L.M + s;
             const int Uj = (a - s) * L.M + s * m + ((s * (s + 1)) >> 1);
@@ -1436,33 +1458,28 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                 const int o = (s - 1 + r) * rs;
 #ifdef CCJ_ABLATE_WHOT
                 // timing only: every W operand load on one cache-resident line (wrong results)
-                v.q[r] = WBW[(lane & 15) + 0 * (o + i - r)];
-                v.p[r] = WBW[(lane & 15) + 16 + 0 * (o + j - s)];
+                v.q[r] = WP[(lane & 15) + 0 * (o + i - r)];
+                v.p[r] = WP[(lane & 15) + 16 + 0 * (o + j - s)];
 #else
-                v.q[r] = WBW[o + i - r];
-                v.p[r] = WBW[o + j - s + 1];
+                v.q[r] = WP[o + i - r];
+                v.p[r] = WP[o + j - s + 1];
 #endif
             }
             return v;
         };
         auto st = [&](const LA &v, int mask) {
-            const int Mm00i = lo16(v.wi.x), Om00i = hi16(v.wi.x), fLi = lo16(v.wi.y), fOi = hi16(v.wi.y);
-            const int Mm00j = lo16(v.wj.x), fLj = lo16(v.wj.y);
-            const int fMpj = lo16(v.wj.z), Kj = hi16(v.wj.z);
+            const int fLi = lo16(v.wi.x), fOi = hi16(v.wi.x);
+            const int fLj = lo16(v.wj.x);
+            const int fMpj = lo16(v.wj.y), Kj = hi16(v.wj.y);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
-                const int wbpi = v.q[r].x, wpi = v.q[r].y, wbi = WBD(wbpi, v.s + r);
-                const int wpj = v.p[r].y, wbj = WBD(v.p[r].x, v.s + r);
+                const int wpi = v.q[r], wpj = v.p[r];
                 int *I = AI_[r], *J = AJ_[r];
-                I[0] = imin(I[0], wbpi + Mm00i);         // PMmloop10 :581-584
-                I[1] = imin(I[1], wbi + Om00i);          // POmloop00 :599-602
-                I[2] = imin(I[2], wbpi + Om00i);         // POmloop10 :632-635
-                I[3] = imin(I[3], fLi + wpi + mask);     // PfromL    :357-359
-                I[4] = imin(I[4], fOi + wpi + mask);     // PfromO    :425-427
-                J[0] = imin(J[0], Mm00j + wbj);          // PMmloop00 :548-551
-                J[1] = imin(J[1], fLj + wpj + mask);     // PfromL    :360-361
-                J[2] = imin(J[2], fMpj + wpj + mask);    // PfromM    :399-401
-                J[3] = imin(J[3], Kj + wpj + mask);      // PK        :184-187
+                I[0] = imin(I[0], fLi + wpi + mask);     // PfromL    :357-359
+                I[1] = imin(I[1], fOi + wpi + mask);     // PfromO    :425-427
+                J[0] = imin(J[0], fLj + wpj + mask);     // PfromL    :360-361
+                J[1] = imin(J[1], fMpj + wpj + mask);    // PfromM    :399-401
+                J[2] = imin(J[2], Kj + wpj + mask);      // PK        :184-187
             }
         };
         if (1 + part <= a) pipe_scan_lead<LA>(1 + part, split, a, a, ld, st);
@@ -1497,15 +1514,11 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             __syncthreads();
         }
         {
-        pMm10 = AI_[0][0];
-        pOm00 = imin(pOm00, AI_[0][1]);
-        pOm10 = AI_[0][2];
-        fL1 = AI_[0][3];
-        fO1 = AI_[0][4];
-        pMm00 = imin(pMm00, AJ_[0][0]);
-        fL2 = AJ_[0][1];
-        fM = AJ_[0][2];
-        pK1 = AJ_[0][3];
+        fL1 = AI_[0][0];
+        fO1 = AI_[0][1];
+        fL2 = AJ_[0][0];
+        fM = AJ_[0][1];
+        pK1 = AJ_[0][2];
         }
         if (!lane_ok || part != 0) return;
 #ifdef CCJ_ABLATE_NOACC  // timing only: no partial-record stores (followers read stale partials)
@@ -1517,19 +1530,17 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             const int tf = t + r;
             if (tf >= T.g_hi) break;
             const int Mf = LD[tf].M, mf = m - r;
-            uint4 *ring = T.acc + (long long)((tf % SHARE_SLOTS) * SHARE_NACC) * T.accC;
+            uint2 *ring = T.acc + (long long)((tf % SHARE_SLOTS) * SHARE_NACC) * T.accC;
             if (i - r >= 1) {
                 const unsigned idx = (unsigned)((a + r) * Mf) + L0 - (unsigned)(r * (h + 1));
                 CHKA(idx);
-                const uint4 v = pack_acc(AI_[r], LA_I);
-                *(uint3 *)(ring + (long long)AI * T.accC + idx) = make_uint3(v.x, v.y, v.z);
+                ((unsigned *)(ring + (long long)AI * T.accC))[idx] = pack_acc(AI_[r], LA_I).x;  // 4-byte records, dense
             }
             if (h - r >= 0) {
                 const int hh = h - r;
                 const unsigned idx = (unsigned)((a + r) * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                const uint4 v = pack_acc(AJ_[r], LA_J);
-                *(uint2 *)(ring + (long long)AJ * T.accC + idx) = make_uint2(v.x, v.y);
+                ring[(long long)AJ * T.accC + idx] = pack_acc(AJ_[r], LA_J);
             }
         }
     };
@@ -1543,31 +1554,25 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     }
     // the ring record of the a-loop: a follower's leader partial (split points a%R+1 .. a)
     if (arole == 2) {
-        const uint4 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
+        const uint2 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
         const unsigned idx = (unsigned)(a * Mt) + L0;
         CHKA(idx);
-        const uint3 pi = *(const uint3 *)(ring + (long long)AI * T.accC + idx);
-        const uint2 pj = *(const uint2 *)(ring + (long long)AJ * T.accC + idx);
-        pMm10 = imin(pMm10, lo16(pi.x));
-        pOm00 = imin(pOm00, hi16(pi.x));
-        pOm10 = imin(pOm10, lo16(pi.y));
-        fL1 = imin(fL1, hi16(pi.y));
-        fO1 = imin(fO1, lo16(pi.z));
-        pMm00 = imin(pMm00, lo16(pj.x));
-        fL2 = imin(fL2, hi16(pj.x));
-        fM = imin(fM, lo16(pj.y));
-        pK1 = imin(pK1, hi16(pj.y));
+        const unsigned pi = ((const unsigned *)(ring + (long long)AI * T.accC))[idx];
+        const uint2 pj = ring[(long long)AJ * T.accC + idx];
+        fL1 = imin(fL1, lo16(pi));
+        fO1 = imin(fO1, hi16(pi));
+        fL2 = imin(fL2, lo16(pj.x));
+        fM = imin(fM, hi16(pj.x));
+        pK1 = imin(pK1, lo16(pj.y));
     }
     // ---- fused b-loop: split point d inside [k, l] ----
-    int pMm01 = INF, pOm01 = INF;
     int fR1 = INF, fR2 = INF, fMp = INF, fO2 = INF, pK2 = INF;
-    struct BV { int2 w2k, w2l; rk_t wk; rec_t wl; int s; };  // raw loads of one split step
+    struct BV { int wpk, wpl; rk_t wk; rl_t wl; };  // raw loads of one split step
     auto load_b = [&](int s) {
         BV v;
-        v.s = s;
         const int r2 = (s - 1) * rs, ll = l - s + 1;
-        v.w2k = WBW[r2 + k];   // (WBP, WP) of (k, k+s-1)
-        v.w2l = WBW[r2 + ll];  // (WBP, WP) of (l-s+1, l)
+        v.wpk = WP[r2 + k];   // WP(k, k+s-1)
+        v.wpl = WP[r2 + ll];  // WP(l-s+1, l)
         CHK(s, a, s, 0);
         CHK(s, a, 0, 0);
 #ifdef CCJ_ABLATE_LOCAL
@@ -1579,32 +1584,24 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Uk = a * L.M + s * m + ((s * (s + 1)) >> 1);  // X(i,j,d,l), d = k+s: lane L0
         const int Ul = a * L.M;                                 // X(i,j,k,d), d = l-s: lane L0 + h*s
         const unsigned lh = L0 + uh * (unsigned)s;
-        // RK at X(i,j,d,l): x = Mm00|fR, y = min(PL,PR)|K
-        // RL at X(i,j,k,d): x = Mm00|Om00, y = Mm10|Om10, z = fR|fO
-        const rec_t *rp = T.rec + L.lr;
-        const rk_t *kp = T.rk + (L.lr >> 1);
-        CHKK((L.lr >> 1) + (unsigned)Uk + L0);
-        CHKR(L.lr + L.C + (unsigned)Ul + lh);
+        // RK at X(i,j,d,l): x = fR|min(PL,PR), y = K|-
+        // RL at X(i,j,k,d): fR|fO
+        const rk_t *kp = T.rk + L.lr;
+        const rl_t *lp = T.rl + L.lr;
+        CHKK(L.lr + (unsigned)Uk + L0);
+        CHKR(L.lr + (unsigned)Ul + lh);
         v.wk = kp[(unsigned)Uk + L0];
-        v.wl = rp[(unsigned)(L.C + Ul) + lh];
+        v.wl = lp[(unsigned)Ul + lh];
         return v;
     };
     // (the PR multiloop family's four terms, :499-537, are not here: 2-D tables, ccj_mloop2d.h)
     auto step_b = [&](const BV &v, int mask) {
-        const int wp_k = v.w2k.y, wbp_l = v.w2l.x, wp_l = v.w2l.y;
-        const int wb_k = WBD(v.w2k.x, v.s), wb_l = WBD(wbp_l, v.s);
-        const int Mm00k = lo16(v.wk.x), fRk = hi16(v.wk.x), PLRk = lo16(v.wk.y), Kk = hi16(v.wk.y);
-        const int Mm00l = lo16(v.wl.x), Om00l = hi16(v.wl.x), Mm10l = lo16(v.wl.y), Om10l = hi16(v.wl.y);
-        const int fRl = lo16(v.wl.z), fOl = hi16(v.wl.z);
-        pMm00 = imin(pMm00, Mm00k + wb_k);                      // :552-555
-        pMm01 = imin(pMm01, Mm00l + wbp_l);                     // :567-570
-        pOm00 = imin(pOm00, Om00l + wb_l);                      // :603-606
-        pOm01 = imin(pOm01, Om00l + wbp_l);                     // :618-621
+        const int wp_k = v.wpk, wp_l = v.wpl;
+        const int fRk = lo16(v.wk.x), PLRk = hi16(v.wk.x), Kk = lo16(v.wk.y);
+        const int fRl = lo16(v.wl), fOl = hi16(v.wl);
         fR1 = imin(fR1, fRk + wp_k + mask);               // PfromR(i,j,d,l) + WP(k,d-1)     :379-381
         fMp = imin(fMp, PLRk + PB + wp_k + mask);         // PfromM'' (:663-679) + WP(k,d-1) :412-414
         pK2 = imin(pK2, Kk + wp_k + mask);                // PK(i,j,d,l) + WP(k,d-1)         :189-192
-        pMm10 = imin(pMm10, Mm10l + wb_l + mask);         // PMmloop10(i,j,k,d) + WB(d+1,l)  :585-588
-        pOm10 = imin(pOm10, Om10l + wb_l + mask);         // POmloop10(i,j,k,d) + WB(d+1,l)  :636-639
         fR2 = imin(fR2, fRl + wp_l + mask);               // PfromR(i,j,k,d) + WP(d+1,l)     :382-383
         fO2 = imin(fO2, fOl + wp_l + mask);               // PfromO(i,j,k,d) + WP(d+1,l)     :429-431
     };
@@ -1620,53 +1617,44 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 #pragma unroll
             for (int f = 0; f < LB_L; ++f) AL_[r][f] = INF;
         }
-        struct LB { rk_t wk; rec_t wl; int2 q[SHARE_R], p[SHARE_R]; int s; };  // raw loads of one split step
+        struct LB { rk_t wk; rl_t wl; int q[SHARE_R], p[SHARE_R]; };  // raw loads of one split step
         auto ld = [&](int s) {
             LB v;
-            v.s = s;
             const LvlDev L = LD[t - s];
             const int Uk = a * L.M + s * m + ((s * (s + 1)) >> 1);
             const int Ul = a * L.M;
             const unsigned lh = L0 + uh * (unsigned)s;
-            const rec_t *rp = T.rec + L.lr;
-            const rk_t *kp = T.rk + (L.lr >> 1);
-            CHKK((L.lr >> 1) + (unsigned)Uk + L0);
-            CHKR(L.lr + L.C + (unsigned)Ul + lh);
+            const rk_t *kp = T.rk + L.lr;
+            const rl_t *lp = T.rl + L.lr;
+            CHKK(L.lr + (unsigned)Uk + L0);
+            CHKR(L.lr + (unsigned)Ul + lh);
             v.wk = kp[(unsigned)Uk + L0];
-            v.wl = rp[(unsigned)(L.C + Ul) + lh];
+            v.wl = lp[(unsigned)Ul + lh];
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
                 const int o = (s - 1 + r) * rs;
 #ifdef CCJ_ABLATE_WHOT
-                v.q[r] = WBW[(lane & 15) + 0 * (o + k - r)];
-                v.p[r] = WBW[(lane & 15) + 16 + 0 * (o + l - s)];
+                v.q[r] = WP[(lane & 15) + 0 * (o + k - r)];
+                v.p[r] = WP[(lane & 15) + 16 + 0 * (o + l - s)];
 #else
-                v.q[r] = WBW[o + k - r];
-                v.p[r] = WBW[o + l - s + 1];
+                v.q[r] = WP[o + k - r];
+                v.p[r] = WP[o + l - s + 1];
 #endif
             }
             return v;
         };
         auto st = [&](const LB &v, int mask) {
-            const int Mm00k = lo16(v.wk.x), fRk = hi16(v.wk.x), PLRk = lo16(v.wk.y), Kk = hi16(v.wk.y);
-            const int Mm00l = lo16(v.wl.x), Om00l = hi16(v.wl.x), Mm10l = lo16(v.wl.y), Om10l = hi16(v.wl.y);
-            const int fRl = lo16(v.wl.z), fOl = hi16(v.wl.z);
+            const int fRk = lo16(v.wk.x), PLRk = hi16(v.wk.x), Kk = lo16(v.wk.y);
+            const int fRl = lo16(v.wl), fOl = hi16(v.wl);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
-                const int wpk = v.q[r].y, wbk = WBD(v.q[r].x, v.s + r);
-                const int wbpl = v.p[r].x, wpl_ = v.p[r].y, wbl = WBD(wbpl, v.s + r);
+                const int wpk = v.q[r], wpl_ = v.p[r];
                 int *K = AK_[r], *Q = AL_[r];
-                K[0] = imin(K[0], Mm00k + wbk);             // PMmloop00 :552-555
-                K[1] = imin(K[1], fRk + wpk + mask);        // PfromR    :379-381
-                K[2] = imin(K[2], PLRk + PB + wpk + mask);  // PfromMprime :412-414
-                K[3] = imin(K[3], Kk + wpk + mask);         // PK        :189-192
-                Q[0] = imin(Q[0], Mm00l + wbpl);            // PMmloop01 :567-570
-                Q[1] = imin(Q[1], Om00l + wbl);             // POmloop00 :603-606
-                Q[2] = imin(Q[2], Om00l + wbpl);            // POmloop01 :618-621
-                Q[3] = imin(Q[3], Mm10l + wbl + mask);      // PMmloop10 :585-588
-                Q[4] = imin(Q[4], Om10l + wbl + mask);      // POmloop10 :636-639
-                Q[5] = imin(Q[5], fRl + wpl_ + mask);       // PfromR    :382-383
-                Q[6] = imin(Q[6], fOl + wpl_ + mask);       // PfromO    :429-431
+                K[0] = imin(K[0], fRk + wpk + mask);        // PfromR    :379-381
+                K[1] = imin(K[1], PLRk + PB + wpk + mask);  // PfromMprime :412-414
+                K[2] = imin(K[2], Kk + wpk + mask);         // PK        :189-192
+                Q[0] = imin(Q[0], fRl + wpl_ + mask);       // PfromR    :382-383
+                Q[1] = imin(Q[1], fOl + wpl_ + mask);       // PfromO    :429-431
             }
         };
         if (1 + part <= b) pipe_scan_lead<LB>(1 + part, split, b, b, ld, st);
@@ -1699,17 +1687,11 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             __syncthreads();
         }
         {
-        pMm00 = imin(pMm00, AK_[0][0]);
-        fR1 = AK_[0][1];
-        fMp = AK_[0][2];
-        pK2 = AK_[0][3];
-        pMm01 = AL_[0][0];
-        pOm00 = imin(pOm00, AL_[0][1]);
-        pOm01 = AL_[0][2];
-        pMm10 = imin(pMm10, AL_[0][3]);
-        pOm10 = imin(pOm10, AL_[0][4]);
-        fR2 = AL_[0][5];
-        fO2 = AL_[0][6];
+        fR1 = AK_[0][0];
+        fMp = AK_[0][1];
+        pK2 = AK_[0][2];
+        fR2 = AL_[0][0];
+        fO2 = AL_[0][1];
         }
         if (!lane_ok || part != 0) return;
 #ifdef CCJ_ABLATE_NOACC
@@ -1721,18 +1703,17 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             const int tf = t + r;
             if (tf >= T.g_hi) break;
             const int Mf = LD[tf].M, mf = m - r;
-            uint4 *ring = T.acc + (long long)((tf % SHARE_SLOTS) * SHARE_NACC) * T.accC;
+            uint2 *ring = T.acc + (long long)((tf % SHARE_SLOTS) * SHARE_NACC) * T.accC;
             if (h - r >= 0) {  // k side
                 const int hh = h - r;
                 const unsigned idx = (unsigned)(a * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                const uint4 v = pack_acc(AK_[r], LB_K);
-                *(uint2 *)(ring + (long long)AK * T.accC + idx) = make_uint2(v.x, v.y);
+                ring[(long long)AK * T.accC + idx] = pack_acc(AK_[r], LB_K);
             }
             if (i <= m - h - r) {  // l side
                 const unsigned idx = (unsigned)(a * Mf) + L0 - (unsigned)(h * r);
                 CHKA(idx);
-                ring[(long long)AL * T.accC + idx] = pack_acc(AL_[r], LB_L);
+                ((unsigned *)(ring + (long long)AL * T.accC))[idx] = pack_acc(AL_[r], LB_L).x;  // 4-byte records, dense
             }
         }
     };
@@ -1745,26 +1726,20 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         pipe_scan<BV>(1 + part, split, b_stop, b, load_b, step_b);
     }
     if (brole == 2) {  // the b-loop's ring record (as for the a-loop)
-        const uint4 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
+        const uint2 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
         const unsigned idx = (unsigned)(a * Mt) + L0;
         CHKA(idx);
-        const uint2 pk = *(const uint2 *)(ring + (long long)AK * T.accC + idx);
-        const uint4 pl = ring[(long long)AL * T.accC + idx];
-        pMm00 = imin(pMm00, lo16(pk.x));
-        fR1 = imin(fR1, hi16(pk.x));
-        fMp = imin(fMp, lo16(pk.y));
-        pK2 = imin(pK2, hi16(pk.y));
-        pMm01 = imin(pMm01, lo16(pl.x));
-        pOm00 = imin(pOm00, hi16(pl.x));
-        pOm01 = imin(pOm01, lo16(pl.y));
-        pMm10 = imin(pMm10, hi16(pl.y));
-        pOm10 = imin(pOm10, lo16(pl.z));
-        fR2 = imin(fR2, hi16(pl.z));
-        fO2 = imin(fO2, lo16(pl.w));
+        const uint2 pk = ring[(long long)AK * T.accC + idx];
+        const unsigned pl = ((const unsigned *)(ring + (long long)AL * T.accC))[idx];
+        fR1 = imin(fR1, lo16(pk.x));
+        fMp = imin(fMp, hi16(pk.x));
+        pK2 = imin(pK2, lo16(pk.y));
+        fR2 = imin(fR2, lo16(pl));
+        fO2 = imin(fO2, hi16(pl));
     }
     if (split > 1) {
         // min-reduce the split waves' partial a/b-loop results; part 0 finishes the cell
-        int acc[SPLIT_RED] = {pMm00, pMm10, pOm00, pOm10, fL1, fL2, fM, fO1, pK1, pMm01, pOm01, fR1, fR2, fMp, fO2, pK2};
+        int acc[SPLIT_RED] = {fL1, fL2, fM, fO1, pK1, fR1, fR2, fMp, fO2, pK2};
         const int cl = wib / split;
         int *slot = red + ((cl * (split - 1) + (part - 1)) * SPLIT_RED) * 64 + lane;
         if (part > 0)
@@ -1777,34 +1752,24 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 #pragma unroll
             for (int x = 0; x < SPLIT_RED; ++x) acc[x] = imin(acc[x], src[x * 64]);
         }
-        pMm00 = acc[0]; pMm10 = acc[1]; pOm00 = acc[2]; pOm10 = acc[3]; fL1 = acc[4]; fL2 = acc[5];
-        fM = acc[6]; fO1 = acc[7]; pK1 = acc[8]; pMm01 = acc[9]; pOm01 = acc[10]; fR1 = acc[11];
-        fR2 = acc[12]; fMp = acc[13]; fO2 = acc[14]; pK2 = acc[15];
+        fL1 = acc[0]; fL2 = acc[1]; fM = acc[2]; fO1 = acc[3]; pK1 = acc[4];
+        fR1 = acc[5]; fR2 = acc[6]; fMp = acc[7]; fO2 = acc[8]; pK2 = acc[9];
         if (!lane_ok) return;
     }
-    // ---- single-step seeds (:566, :580), level t-1 (PRmloop01 / 10's, :519 / :533, are in the tables)
-    int vPMm01 = pMm01, vPMm10 = pMm10;
-    {
-        if (t >= 1) {
-            const LvlDev L = LD[t - 1];
-            const int16_t *lp = D4 + L.lb;
-            if (b >= 1) vPMm01 = imin(vPMm01, LDX(lp, L, PMmloop01, a * L.M + m + 1, L0) + cp);       // (i,j,k+1,l)
-            // PMmloop10 from the RL record (IN_REC, ccj_engine.h carrier: not read from d4)
-            if (a >= 1) vPMm10 = imin(vPMm10, lo16(T.rec[L.lr + (unsigned)(L.C + (a - 1) * L.M + m + 1) + L0].y) + cp);  // (i,j-1,k,l)
-        }
-    }
-    const int vPMm00 = pMm00;
-    const int vPOm00 = pOm00, vPOm01 = pOm01, vPOm10 = pOm10;
     // the PL / PR multiloop tables (ccj_mloop2d.h), span-major: consecutive lanes (i) read consecutive
     // words.  get_PLmloop / get_PRmloop read spans a-2 / b-2 <= t-2 (written by k_diag2d(<= t-2))
     const int16_t *__restrict__ TAB = T.tab;
     const long long tabN = T.tabN;
+    // the PM / PO closed-form tables (ccj_pmpo2d.h), span-major like them: get_PMmloop / get_POmloop
+    // evaluate the 10 / 01 values of a level t-2 cell from spans a-1 / b-1 <= t-1 (k_diag2d(<= t-1))
+    const int *__restrict__ CF = T.cf;
+    const int cf_s = pmpo2d_seed(bp);
 
     // ---- level t-2 neighbours of PL/PR/PM/PO (stack terms, get_P?mloop, PfromX)
     const LvlDev L2 = LD[t >= 2 ? t - 2 : 0];
     const int16_t *lp2 = D4 + L2.lb;
-    // the record-carried matrices of those neighbours (PfromL, PfromR, PMmloop10, POmloop10, PfromO;
-    // IN_REC, ccj_engine.h carrier) from their loop records: one 12-byte load per cell
+    // the record-carried matrices of those neighbours (PfromL, PfromR, PfromO; IN_REC, ccj_engine.h
+    // carrier) from their loop records
     const rec_t *rp2 = T.rec + L2.lr;
     // own slots of level t: k_iloop(t) left the interior-loop minima of PL/PR/PM there
     const LvlDev Lt = LD[t];
@@ -1828,7 +1793,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         // get_PLmloop (:705-715): PLmloop10 / PLmloop01 of (i+1, j-1), table span a-2
         const int ot = (a - 2) * rs + i + 1;
         const int b2 = (a >= 2) ? imin((int)TAB[2 * tabN + ot], (int)TAB[1 * tabN + ot]) + apbp2 : INF;
-        const int b3 = (a >= TURN + 1) ? lo16(rp2[(unsigned)Uin + L0 + uh].y) : INF;  // RA: ., fL|., .
+        const int b3 = (a >= TURN + 1) ? lo16(rp2[(unsigned)Uin + L0 + uh].x) : INF;  // RA: fL|., .
         vPL = imin(imin(b1, b2), b3);
     }
     // ---- PR (:255-275) with get_PRiloop (:717-738, k_iloop), get_PRmloop (:740-750)
@@ -1847,7 +1812,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         // get_PRmloop (:740-750): PRmloop10 / PRmloop01 of (k+1, l-1), table span b-2
         const int ot = (b - 2) * rs + k + 1;
         const int b2 = (b >= 2) ? imin((int)TAB[5 * tabN + ot], (int)TAB[4 * tabN + ot]) + apbp2 : INF;
-        const int b3 = (b >= TURN + 1) ? hi16(T.rk[(L2.lr >> 1) + (unsigned)Uin + L0 + uh].x) : INF;  // RK: .|fR, .
+        const int b3 = (b >= TURN + 1) ? lo16(T.rl[L2.lr + (unsigned)Uin + L0 + uh]) : INF;  // RL: fR|.
         vPR = imin(imin(b1, b2), b3);
     }
     // ---- PM (:277-300) with get_PMiloop (:752-773, k_iloop), get_PMmloop (:775-785)
@@ -1864,7 +1829,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             if (a >= 2 && b >= 2) b1 = imin(b1, imin(pin + W2E(T.ie, j - 1, k + 1), (int)dst[mslot(PM) * C]));
 #endif
         }
-        const int b2 = inner ? imin(lo16(rp2[(unsigned)(L2.C + Uin) + L0].y), LDX(lp2, L2, PMmloop01, Uin, L0)) + apbp2 : INF;  // RL: ., Mm10|., .
+        // get_PMmloop (:775-785): PMmloop10 / PMmloop01 of (i, j-1, k+1, l) in closed form, table
+        // entries (i, j-1) of span a-1 and (k+1, l) of span b-1
+        int b2 = INF;
+        if (inner) {
+            const int oij = (a - 1) * rs + i, okl = (b - 1) * rs + k + 1;
+            const int m10 = pmpo2d_PMmloop10(cf_s, cp, a - 1, CF[CF_UP * tabN + oij], CF[CF_Z * tabN + okl], CF[CF_CL * tabN + okl]);
+            const int m01 = pmpo2d_PMmloop01(cf_s, cp, b - 1, CF[CF_A * tabN + oij], CF[CF_Y * tabN + okl]);
+            b2 = imin(m10, m01) + apbp2;
+        }
         const int b3 = inner ? LDX(lp2, L2, PfromM, Uin, L0) : INF;
         const int b4 = (a == 0 && b == 0) ? 0 : INF;
         vPM = imin(imin(b1, b2), imin(b3, b4));
@@ -1876,13 +1849,19 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
         const int Uin = (a - 1) * L2.M + 1;  // (i+1, j, k, l-1): lane L0 + 2h
         int b1 = INF;
         if (l - i > TURN && inner) b1 = LDX(lp2, L2, PO, Uin, L0 + 2 * uh) + W2E(T.est, i, l);
-        const rec_t rl = inner ? rp2[(unsigned)(L2.C + Uin) + L0 + 2 * uh] : make_uint3(0, 0, 0);  // RL: ., .|Om10, .|fO
-        const int b2 = inner ? imin(hi16(rl.y), LDX(lp2, L2, POmloop01, Uin, L0 + 2 * uh)) + apbp2 : INF;
-        const int b3 = (inner && l - i >= TURN + 1) ? hi16(rl.z) : INF;
+        // get_POmloop (:810-820): POmloop10 / POmloop01 of (i+1, j, k, l-1) in closed form, table
+        // entries (i+1, j) of span a-1 and (k, l-1) of span b-1
+        int b2 = INF;
+        if (inner) {
+            const int oij = (a - 1) * rs + i + 1, okl = (b - 1) * rs + k;
+            const int m10 = pmpo2d_POmloop10(cf_s, CF[CF_UO * tabN + oij], CF[CF_ZO * tabN + okl], CF[CF_CL * tabN + okl]);
+            const int m01 = pmpo2d_POmloop01(cf_s, CF[CF_AO * tabN + oij], CF[CF_XO * tabN + okl]);
+            b2 = imin(m10, m01) + apbp2;
+        }
+        const int b3 = (inner && l - i >= TURN + 1) ? hi16(T.rl[L2.lr + (unsigned)Uin + L0 + 2 * uh]) : INF;  // RL: .|fO
         vPO = imin(imin(b1, b2), b3);
     }
 #undef LDX
-#undef WBD
 #undef CHK
 #undef CHKR
 #undef CHKA
@@ -1905,25 +1884,18 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     dst[mslot(PM) * C] = (int16_t)sPM;
     dst[mslot(PO) * C] = (int16_t)sPO;
     // the IN_D4 matrices always, the IN_REC ones only where d4 has their slots (ccj_engine.h carrier;
-    // the IN_TAB ones never: ccjk_expand writes them out after the fill where a reader wants them)
+    // the IN_TAB and IN_CF ones never: ccjk_expand writes them out where a reader wants them)
     if (T.full4) dst[mslot(PfromL) * C] = (int16_t)clamp_store(vPfromL);
     if (T.full4) dst[mslot(PfromR) * C] = (int16_t)clamp_store(vPfromR);
     dst[mslot(PfromM) * C] = (int16_t)clamp_store(vPfromM);
     if (T.full4) dst[mslot(PfromMprime) * C] = (int16_t)clamp_store(vPfromMp);
     if (T.full4) dst[mslot(PfromO) * C] = (int16_t)clamp_store(vPfromO);
-    if (T.full4) dst[mslot(PMmloop00) * C] = (int16_t)clamp_store(vPMm00);
-    dst[mslot(PMmloop01) * C] = (int16_t)clamp_store(vPMm01);
-    if (T.full4) dst[mslot(PMmloop10) * C] = (int16_t)clamp_store(vPMm10);
-    if (T.full4) dst[mslot(POmloop00) * C] = (int16_t)clamp_store(vPOm00);
-    dst[mslot(POmloop01) * C] = (int16_t)clamp_store(vPOm01);
-    if (T.full4) dst[mslot(POmloop10) * C] = (int16_t)clamp_store(vPOm10);
     // loop records and interior-loop copies (the copies only where a later k_iloop can read them:
     // its pair can pair); in sharded fills the other ranks' cells get both from k_unpack
     if (!copies) return;
 #ifndef CCJ_ABLATE_NOREC  // timing only: no loop-record stores (the split loops then read stale records)
-    write_records(T, Lt.lr, C, (unsigned)(a * Mt) + L0, clamp_store(vPMm00), clamp_store(vPOm00), clamp_store(vPfromL),
-                  clamp_store(vPfromO), clamp_store(vPfromMp), clamp_store(vPK), clamp_store(vPfromR), imin(sPL, sPR),
-                  clamp_store(vPMm10), clamp_store(vPOm10));
+    write_records(T, Lt.lr + (long long)((unsigned)(a * Mt) + L0), clamp_store(vPfromL), clamp_store(vPfromO),
+                  clamp_store(vPfromMp), clamp_store(vPK), clamp_store(vPfromR), imin(sPL, sPR));
 #endif
 #ifdef CCJ_ABLATE_NOCOPY
     return;  // timing only: no interior-loop copies (k_iloop then reads stale values)
@@ -1942,12 +1914,13 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 __global__ __launch_bounds__(512) void k_level4d(DevTables T, int t, int wavesPerA, int split, int G, int rank, int nblk, int copies) {
     level4d_body<false>(T, t, wavesPerA, split, G, rank, nblk, copies);
 }
-// The leader launch is held at 3 waves per SIMD.  Since the PL / PR multiloop terms left, it would
-// fit 4 (123 VGPRs instead of 132), and 4 measured slower at n=200: step 33.3 ms against 32.5 ms
-// with 3, and faster at n=400, 570 ms against 583 ms (parent: 34.4 / 627 ms; DESIGN.md §4,
-// profiles/mloop2d_ab.txt).  -DCCJ_LEAD_WAVES=0 lifts the limit, =k sets another (A/B builds).
+// The leader launch is held at 4 waves per SIMD.  Since the PM / PO multiloop terms left it needs 68
+// VGPRs (122 before) and would fit 7; alternating at n=200 / n=400 (profiles/pmpo_ab.txt): 3 waves
+// 28.0-28.2 / 448-450 ms, 4 waves 27.9-28.1 / 431-432 ms (ahead in every pair), 5 waves 28.8-29.0 /
+// 429-431 ms, no limit 28.5-28.7 / 439-440 ms.  -DCCJ_LEAD_WAVES=0 lifts the limit, =k sets another
+// (A/B builds).
 #ifndef CCJ_LEAD_WAVES
-#define CCJ_LEAD_WAVES 3
+#define CCJ_LEAD_WAVES 4
 #endif
 #if CCJ_LEAD_WAVES > 0
 __attribute__((amdgpu_waves_per_eu(CCJ_LEAD_WAVES, CCJ_LEAD_WAVES)))
@@ -1974,8 +1947,9 @@ extern "C" int ccjk_precompute_ie(const DevTables *T, void *stream) {
 extern "C" int ccjk_diag2d(const DevTables *T, int sigma, int G, int rank, void *stream) {
     const int nint = T->n - sigma;  // intervals of the span; rank takes i = rank+1, rank+1+G, ...
     const int nb = nint > rank ? (nint - rank + G - 1) / G : 0;
-    // + the span's PL / PR multiloop tables, one wave per interval (every interval on every rank)
-    const int ntab = nint > 0 ? (nint + 3) / 4 : 0;
+    // + the span's PL / PR multiloop tables and PM / PO closed-form tables, one wave per interval and
+    // family (every interval on every rank)
+    const int ntab = nint > 0 ? (2 * nint + 3) / 4 : 0;
     if (nb + ntab <= 0) return 0;
     hipLaunchKernelGGL(k_diag2d, dim3(nb + ntab), dim3(256), 0, (hipStream_t)stream, *T, sigma, G, rank, nb);
     return (int)hipGetLastError();
@@ -2097,8 +2071,10 @@ __global__ __launch_bounds__(256) void k_pack(DevTables T, int t, int G, int r, 
     const LvlDev Lt = T.ld[t];
     const int16_t *src = T.d4 + Lt.lb + (long long)shard_a(xch_own(k, part), G, r) * Mt + c;
 #pragma unroll 2
-    for (int x = 0; x < NMAT4; ++x)  // the six table-carried matrices keep their place in the slice, unused (32767)
-        send[xch_pos(x, k, c, nmax, Mt)] = carrier(x) == IN_TAB ? (int16_t)INTERN_INF : src[(long long)mslot(x) * Lt.C];
+    for (int x = 0; x < NMAT4; ++x) {  // the table-carried and closed-form matrices keep their place in the slice, unused (32767)
+        const bool own = carrier(x) == IN_D4 || carrier(x) == IN_REC;
+        send[xch_pos(x, k, c, nmax, Mt)] = own ? src[(long long)mslot(x) * Lt.C] : (int16_t)INTERN_INF;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r, int part, int nmax, const int16_t *recv,
@@ -2123,12 +2099,11 @@ __global__ __launch_bounds__(256) void k_unpack(DevTables T, int t, int G, int r
     const int16_t *sl = recv + (size_t)ro * rstride;
 #pragma unroll
     for (int x = 0; x < NMAT4; ++x) {
-        if (carrier(x) == IN_TAB) continue;  // every rank computes the tables itself (ccj_mloop2d.h)
+        if (carrier(x) == IN_TAB || carrier(x) == IN_CF) continue;  // every rank computes the tables itself (ccj_mloop2d.h, ccj_pmpo2d.h)
         v[x] = sl[xch_pos(x, k, c, nmax, Mt)];
         dst[mslot(x) * C] = (int16_t)v[x];
     }
-    write_records(T, Lt.lr, Lt.C, (unsigned)(a * Mt + c), v[PMmloop00], v[POmloop00], v[PfromL], v[PfromO], v[PfromMprime],
-                  v[PK], v[PfromR], imin(v[PL], v[PR]), v[PMmloop10], v[POmloop10]);
+    write_records(T, Lt.lr + (long long)(a * Mt + c), v[PfromL], v[PfromO], v[PfromMprime], v[PK], v[PfromR], imin(v[PL], v[PR]));
     if (ptype(T, i, j) > 0) T.d4x[X.lbx + (long long)a * Mt + (i - 1) * m - (((i - 1) * (i - 2)) >> 1) + h] = (int16_t)v[PL];
     if (ptype(T, kk, l) > 0) {
         const int q = i + h - 1;

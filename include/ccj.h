@@ -240,6 +240,13 @@ void ccj_destroy(ccj_ctx *ctx);
 /* Number of 4-D DP cells (unit of work): C(n+1,4). */
 uint64_t ccj_num_cells(int n);
 
+/* The closed forms of the PM / PO multiloop families on the host, no GPU: from the
+ * raw WBP of a sequence (row-major (n+1) x (n+1), entry i*(n+1)+j, 1 <= i <= j <= n) and bp, cp, the
+ * stored values of PMmloop00/01/10 and POmloop00/01/10 (in that order, `cells` values each) of every
+ * valid cell in the order i, j >= i, k >= j+2, l >= k (l fastest).  Returns the cells per matrix
+ * (out may be NULL to count), or -1. */
+long long ccj_pmpo2d_closed(int n, const int *wbp, int bp, int cp, int16_t *out, long long cells);
+
 #ifdef __cplusplus
 }
 #endif
