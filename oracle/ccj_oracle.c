@@ -56,6 +56,9 @@ typedef struct oracle {
        eint[(p*(n+2)+q)*29*29 + u1*29 + u2] = lrint(e_intP * E_IntLoop) for the outer pair (p,q)
        and the inner pair (p+1+u1, q-1-u2); the same value the reference recomputes per candidate */
     int *eint;
+    /* 4-D stores whose value lay below -32768 before the int16 assignment of set4 (there the
+       reference's store wraps, matrices.hh:188-191, and this restatement wraps with it) */
+    long long low_stores;
 } oracle;
 
 /* matrix ids, reference allocate_space order (pseudo_loop.cc:37-62) */
@@ -198,6 +201,10 @@ static inline int get4(const oracle *o, int m, int i, int j, int k, int l) { /* 
 }
 static inline void set4(oracle *o, int m, int i, int j, int k, int l, int e) { /* matrices.hh:188-191 */
     if (e >= INTERN_INF) e = INTERN_INF;
+    if (e < INT16_MIN) { /* rare; the cells of one level store from many threads */
+#pragma omp atomic
+        o->low_stores++;
+    }
     o->M4[m][idx4(o, i, j, k, l)] = (int16_t)e;
 }
 
@@ -877,6 +884,8 @@ void ccj_oracle_free(oracle *o) {
 
 int ccj_oracle_n(const oracle *o) { return o->n; }
 int ccj_oracle_W(const oracle *o, int j) { return o->W[j]; }
+/* 0: every 4-D value of this fold was stored inside the int16 range (no store wrapped) */
+long long ccj_oracle_low_stores(const oracle *o) { return o->low_stores; }
 
 /* reference getter semantics (matrices.hh:177-182) */
 int ccj_oracle_get4(const oracle *o, int m, int i, int j, int k, int l) { return get4(o, m, i, j, k, l); }

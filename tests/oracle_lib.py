@@ -35,7 +35,7 @@ def oracle_lib():
         if not os.path.exists(ORACLE_SO):
             subprocess.run(make, capture_output=True)
         L = ctypes.CDLL(ORACLE_SO) if os.path.exists(ORACLE_SO) else None
-        if L is None or not hasattr(L, "ccj_oracle_fold_par_pen"):
+        if L is None or not hasattr(L, "ccj_oracle_low_stores"):
             # oracle/_ref cannot be written, or holds a library left over from an older
             # ccj_oracle.c (whatever its timestamp says, whoever owns it): build the current source
             # into a directory of our own and load that file; dlopen() would hand back the image it
@@ -65,6 +65,8 @@ def oracle_lib():
         L.ccj_oracle_get2.restype = ctypes.c_int
         L.ccj_oracle_W.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.ccj_oracle_W.restype = ctypes.c_int
+        L.ccj_oracle_low_stores.argtypes = [ctypes.c_void_p]
+        L.ccj_oracle_low_stores.restype = ctypes.c_longlong
         _lib = L
     return _lib
 
@@ -104,6 +106,12 @@ class OracleFold:
 
     def W(self, j):
         return oracle_lib().ccj_oracle_W(self.h, j)
+
+    def low_stores(self):
+        """4-D stores of this fold whose value lay below -32768 before the reference's int16
+        assignment (matrices.hh:188-191), where it wraps.  0: the fold lies inside the domain in
+        which the engine is bit-identical to the reference."""
+        return oracle_lib().ccj_oracle_low_stores(self.h)
 
     def close(self):
         if self.h:
