@@ -19,7 +19,7 @@ from typing import Optional
 __all__ = [
     "W_final", "ccj", "load_params", "load_par", "ParFileError", "param_path", "CCJError", "BacktrackExit", "lib", "MAT4", "MAT2",
     "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
-    "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2",
+    "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw",
 ]
 
@@ -130,6 +130,16 @@ def lib() -> ctypes.CDLL:
         getattr(L, fn).restype = ip
     L.ccj_reset.argtypes = [vp, cp]
     L.ccj_reset.restype = ip
+    L.ccj_create_cap.argtypes = [ctypes.POINTER(_Problem), ctypes.POINTER(_Options), ip, ctypes.POINTER(vp)]
+    L.ccj_create_cap.restype = ip
+    L.ccj_rebind.argtypes = [vp, cp]
+    L.ccj_rebind.restype = ip
+    L.ccj_capacity.argtypes = [vp]
+    L.ccj_capacity.restype = ip
+    L.ccj_layout_extents.argtypes = [ip, ip, ip, ip, ip, ctypes.POINTER(ctypes.c_longlong), ip]
+    L.ccj_layout_extents.restype = ip
+    L.ccj_layout_extent_names.argtypes = []
+    L.ccj_layout_extent_names.restype = cp
     L.ccj_fill_async.argtypes = [vp]
     L.ccj_fill_async.restype = ip
     L.ccj_fill_async_after.argtypes = [vp, vp]
@@ -314,7 +324,7 @@ class W_final:
                  noGU: bool = False, device: int = 0, overlap_d2h: bool = False, shard_world: int = 1,
                  shard_rank: int = 0, shard_simulate: bool = False, comm_id: Optional[bytes] = None,
                  host_traceback: bool = False, split_target: int = 0, share_splits: int = 0,
-                 local_group: Optional["LocalGroup"] = None, pen=None):
+                 local_group: Optional["LocalGroup"] = None, pen=None, capacity: Optional[int] = None):
         """shard_world > 1: band-shard this one sequence over shard_world processes (one per GPU),
         exchanging each level over RCCL; every rank passes the same comm_id (from comm_unique_id()
         on one rank), or the same local_group when the ranks are contexts of this process.
@@ -325,7 +335,9 @@ class W_final:
         < 0 = never split a level / no split-point sharing).
         pen: the pseudoknot penalties (include/ccj_params.h ccj_pk_penalties), 14 values in the
         struct's order: PS PSM PSP PB PUP PPS a b c ap bp cp (ints) e_stP e_intP (floats); None =
-        the reference's h_globals.hh defaults (PEN_DEFAULT)."""
+        the reference's h_globals.hh defaults (PEN_DEFAULT).
+        capacity: allocate for every length 1 .. capacity (include/ccj.h ccj_create_cap), so that
+        rebind() can bind sequences of other lengths; None = the length of seq."""
         self.seq = seq
         self.n = len(seq)
         self.dangle = dangle
@@ -344,7 +356,10 @@ class W_final:
         opts = _Options(device, 1 if overlap_d2h else 0, shard_world, shard_rank, 1 if shard_simulate else 0,
                         1 if host_traceback else 0, split_target, share_splits)
         h = ctypes.c_void_p()
-        rc = L.ccj_create(ctypes.byref(prob), ctypes.byref(opts), ctypes.byref(h))
+        if capacity is None:
+            rc = L.ccj_create(ctypes.byref(prob), ctypes.byref(opts), ctypes.byref(h))
+        else:
+            rc = L.ccj_create_cap(ctypes.byref(prob), ctypes.byref(opts), int(capacity), ctypes.byref(h))
         if rc != CCJ_OK:
             raise CCJError(rc, L.ccj_last_error(None).decode())
         self._h = h
@@ -370,6 +385,22 @@ class W_final:
         self.structure = None
         self.energy = None
         self.stdout_msgs = ""
+
+    def rebind(self, seq: str) -> None:
+        """Bind this context to another sequence of any length up to its capacity (include/ccj.h
+        ccj_rebind): nothing is allocated; with the bound length it is reset()."""
+        self._check(lib().ccj_rebind(self._h, seq.encode()))
+        self.seq = seq
+        self.n = len(seq)
+        self._seq_buf = ctypes.create_string_buffer(seq.encode())
+        self.structure = None
+        self.energy = None
+        self.stdout_msgs = ""
+
+    @property
+    def capacity(self) -> int:
+        """The longest sequence this context can be bound to (ccj_capacity)."""
+        return lib().ccj_capacity(self._h)
 
     def _check(self, rc: int):
         if rc != CCJ_OK:
@@ -553,6 +584,69 @@ def level_schedule(n: int, t: int, world: int = 1, rank: int = 0, split_target: 
     if rc != CCJ_OK:
         raise CCJError(rc, "bad schedule arguments")
     return LevelSchedule((bool(out[0]), out[1], out[2], out[3], out[4]))
+
+
+def layout_extents(n: int, split_target: int = DEFAULT_SPLIT_TARGET, share: bool = True, full4: bool = False,
+                   as_capacity: bool = False) -> dict:
+    """Element counts of every device buffer whose size depends on n (no GPU needed; include/ccj.h
+    ccj_layout_extents): what a binding of n uses, or with as_capacity what a context of capacity n
+    allocates.  split_target is the resolved target (0 = never split)."""
+    L = lib()
+    names = L.ccj_layout_extent_names().decode().split()
+    out = (ctypes.c_longlong * len(names))()
+    got = L.ccj_layout_extents(n, split_target, 1 if share else 0, 1 if full4 else 0, 1 if as_capacity else 0, out, len(names))
+    if got != len(names):
+        raise CCJError(CCJ_E_ARG, "bad layout arguments")
+    return dict(zip(names, out))
+
+
+def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False, device: int = 0,
+              contexts: int = 2, capacity: Optional[int] = None, pen=None, **engine) -> list:
+    """Fold sequences of mixed lengths through `contexts` capacity contexts (capacity: the longest
+    sequence by default), kept in flight with rebind + fill_async / wait: while one context's
+    traceback runs, the next context's fill has the GPU.  Returns one record per sequence, in input
+    order: (seq, structure, energy, stdout_msgs, exit_code, stderr).  A reference backtrack exit is
+    a record with structure and energy None, its exit code and stderr text; it does not disturb the
+    other folds.  engine: further W_final options (split_target, share_splits, host_traceback, ...)."""
+    seqs = list(seqs)
+    if not seqs:
+        return []
+    cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
+    k = max(1, min(int(contexts), len(seqs)))
+    out: list = [None] * len(seqs)
+    ctx: list = []      # the contexts, created on their first sequence
+    flying: list = []   # (context, input index) in enqueue order
+
+    def finish(wf, x):
+        try:
+            e = wf.wait()
+            out[x] = (seqs[x], wf.structure, e, wf.stdout_msgs, 0, "")
+        except BacktrackExit as ex:
+            out[x] = (seqs[x], None, None, ex.stdout, ex.exit_code, ex.msg)
+
+    try:
+        for x, s in enumerate(seqs):
+            if len(ctx) < k:
+                wf = W_final(s, dangle, params=params, noGU=noGU, device=device, pen=pen, capacity=cap, **engine)
+                ctx.append(wf)
+            else:
+                wf, done = flying.pop(0)  # the oldest fold in flight: its context is the next free one
+                finish(wf, done)
+                wf.rebind(s)
+            wf.fill_async()
+            flying.append((wf, x))
+        while flying:
+            wf, done = flying.pop(0)
+            finish(wf, done)
+    finally:
+        for wf, _ in flying:  # an error above: let the folds in flight end before their contexts close
+            try:
+                wf.wait()
+            except CCJError:
+                pass
+        for wf in ctx:
+            wf.close()
+    return out
 
 
 def ccj(seq: str, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False,

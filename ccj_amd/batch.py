@@ -1,0 +1,92 @@
+"""Fold a file of sequences of mixed lengths through a few capacity contexts (ccj_amd.fold_many).
+
+    python -m ccj_amd.batch [-d N] [-P set] [--noGU] [--contexts K] FILE
+
+FILE holds one sequence per line, or FASTA records (a '>' header line, then the sequence over one
+or more lines); '-' reads standard input.  Sequences are upper-cased and T becomes U, as the CCJ
+command line does (ccj_amd/cli.py).  For every sequence, in input order, stdout gets exactly what
+one CCJ run prints for it (cli.fold_cli: side messages, the sequence, "STRUCT (E)"; only the side
+messages where the reference's backtrack exits) and stderr its stderr text; a sequence with a
+character outside GCAU gets the command line's message and counts as exit code 1.  The exit code is
+the largest one seen.  -P names a bundled parameter set or a .ccjp / .par path (default
+DirksPierce09).  Device: $CCJ_DEVICE, else $LOCAL_RANK, else 0.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+from . import fold_many, load_params
+from .cli import fmt_energy
+
+
+def read_sequences(lines) -> list:
+    """One sequence per line, or FASTA; blank lines separate nothing and are skipped."""
+    seqs, cur, fasta = [], None, False
+    for raw in lines:
+        line = raw.strip()
+        if not line:
+            continue
+        if line.startswith(">"):
+            fasta = True
+            if cur:
+                seqs.append(cur)
+            cur = ""
+        elif fasta:
+            cur = (cur or "") + line
+        else:
+            seqs.append(line)
+    if cur:
+        seqs.append(cur)
+    return [s.upper().replace("T", "U") for s in seqs]
+
+
+def record_stdout(rec) -> str:
+    """What cli.fold_cli returns as stdout for one fold_many record."""
+    seq, structure, energy, msgs, code, _ = rec
+    if structure is None:
+        return msgs
+    return msgs + seq + "\n" + f"{structure} ({fmt_energy(energy)})\n"
+
+
+def run(argv=None, stdout=None, stderr=None) -> int:
+    stdout = stdout or sys.stdout
+    stderr = stderr or sys.stderr
+    ap = argparse.ArgumentParser(prog="python -m ccj_amd.batch", description=__doc__.splitlines()[0])
+    ap.add_argument("-d", "--dangles", type=int, default=2)
+    ap.add_argument("-P", "--paramFile", default="DirksPierce09")
+    ap.add_argument("--noGU", action="store_true")
+    ap.add_argument("--contexts", type=int, default=2)
+    ap.add_argument("file")
+    a = ap.parse_args(argv)
+    if a.file == "-":
+        seqs = read_sequences(sys.stdin)
+    else:
+        with open(a.file) as f:
+            seqs = read_sequences(f)
+    bad = {}
+    for x, s in enumerate(seqs):
+        c = next((c for c in s if c not in "GCAU"), None)
+        if c is not None:
+            bad[x] = f"Sequence contains character {c} that is not G,C,A,U, or T.\n"
+    good = [s for x, s in enumerate(seqs) if x not in bad]
+    device = int(os.environ.get("CCJ_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    recs = iter(fold_many(good, a.dangles, params=load_params(a.paramFile), noGU=a.noGU, device=device,
+                          contexts=a.contexts))
+    code = 0
+    for x in range(len(seqs)):
+        if x in bad:
+            stdout.write(bad[x])
+            code = max(code, 1)
+            continue
+        rec = next(recs)
+        stdout.write(record_stdout(rec))
+        stderr.write(rec[5])
+        code = max(code, rec[4])
+    stdout.flush()
+    return code
+
+
+if __name__ == "__main__":
+    sys.exit(run())

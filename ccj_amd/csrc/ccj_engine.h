@@ -444,4 +444,9 @@ int ccjk_items(const ccj::DevTables *T, int G, int rank, int simulate, long long
                uint32_t *items, int pass, void *stream);
 int ccjk_canon(const ccj::DevTables *T, int x, const long long *offij, int16_t *out, void *stream);
 int ccjk_expand(const ccj::DevTables *T, int t, int first_slot, int16_t *out, void *stream);
+// The n-dependent device state of a binding (k_bind_layout): the nent = max(n, 1) level descriptors
+// (lv, lb, ld, ldx) from T->n, T->d4, T->xpad and nm4, and 32767 over x_cnt elements from x_fill and
+// pm_cnt from pm_fill (16-byte aligned; 0: no fill).
+int ccjk_bind_layout(const ccj::DevTables *T, int nent, int nm4, ccj::LevelDesc *lv, long long *lb, ccj::LvlDev *ld,
+                     ccj::LvlX *ldx, int16_t *x_fill, long long x_cnt, int16_t *pm_fill, long long pm_cnt, void *stream);
 }

@@ -124,6 +124,12 @@ struct ccj_ctx {
     bool full4 = false;                 // a full context: d4 has all 22 slots per level (DevTables::full4)
     int nm4 = NMAT_D4;                  // matrix slots per level in d4 (NMAT4 when full4; ccj_engine.h mslot)
     int nlev = 0;                       // levels with cells (0..n-3)
+    // capacity (ccj_create_cap): the allocations hold any binding of 1 <= n <= ncap; cap_ext = their
+    // element counts (ccj_layout_extents, as_capacity = 1)
+    int ncap = 0;
+    std::vector<long long> cap_ext;
+    void *h_bind = nullptr;             // pinned staging of the leader lists (bind_layout)
+    hipEvent_t ev_bind = nullptr;       // their upload has read the staging
 
     // device
     int16_t *d4 = nullptr;
@@ -545,9 +551,19 @@ static int local_bulk_wait_copied(ccj_ctx *c) {
     return CCJ_OK;
 }
 
+// element counts of the n-dependent buffers (layout_extents below; ccj_layout_extents)
+enum LayoutExtent {
+    LX_D4, LX_REC, LX_RK, LX_RL, LX_ACC, LX_D4X, LX_PMX, LX_LORD, LX_LORD_OFF, LX_PLANE, LX_IL, LX_ILSEG,
+    LX_LEVELS, LX_LXTAB, LX_EVENTS, LX_ICOUNT, LX_PPUSH_SPAN, LX_ILOOP_SPAN, LX_N
+};
+static const char *const LX_NAMES =
+    "d4 rec rk rl acc d4x pmx lord lord_off plane il ilseg levels lx events icount ppush_span iloop_span";
+constexpr long long X_EDGE = 256;  // sentinel elements on either side of the interior-loop copies
+
 // Everything that depends on the sequence itself (not only on n): the encoding, the pair-type,
-// hairpin and e_stP tables, and the k_iloop work items.  ccj_create runs it once, ccj_reset for
-// each new sequence of the same length (the allocations are reused).
+// hairpin and e_stP tables, and the k_iloop work items.  ccj_create runs it once, ccj_reset and
+// ccj_rebind for each new sequence (the allocations are reused; a rebind to another length lays
+// the buffers out anew first, bind_layout).
 static int seq_setup(ccj_ctx *c) {
     ccj_ctx *cp = c;
     const int n = c->n;
@@ -607,8 +623,9 @@ static int seq_setup(ccj_ctx *c) {
     lap("pair types");
     // the sequence tables go up asynchronously on st from pinned staging (a reset never blocks on
     // work another context has running on the GPU); the fill's launches follow on st
-    const size_t stage_bytes = plane * (1 + sizeof(int) + sizeof(int16_t)) + 2 * (size_t)(n + 2) * sizeof(short);
-    if (!c->h_stage) {
+    if (!c->h_stage) {  // sized for the capacity, like every allocation (create_impl)
+        const size_t stage_bytes = (size_t)c->cap_ext[LX_PLANE] * (1 + sizeof(int) + sizeof(int16_t)) +
+                                   2 * (size_t)(c->ncap + 2) * sizeof(short);
         HIPCHK(cp, hipHostMalloc(&c->h_stage, stage_bytes, hipHostMallocDefault));
         HIPCHK(cp, hipEventCreateWithFlags(&c->ev_stage, hipEventDisableTiming));
     } else {
@@ -645,7 +662,7 @@ static int seq_setup(ccj_ctx *c) {
         static const bool host_count = getenv("CCJ_HOST_COUNT") && atoi(getenv("CCJ_HOST_COUNT")) != 0;
         if (!host_count) {
             HIPCHK(cp, (hipError_t)ccjk_items(&c->T, G, c->rank, c->simulate, c->d_icount, nullptr, nullptr, 0, c->st));
-            if (!c->h_icount) HIPCHK(cp, hipHostMalloc(&c->h_icount, cnt2.size() * sizeof(long long), hipHostMallocDefault));
+            if (!c->h_icount) HIPCHK(cp, hipHostMalloc(&c->h_icount, (size_t)c->cap_ext[LX_ICOUNT] * sizeof(long long), hipHostMallocDefault));
             HIPCHK(cp, hipMemcpyAsync(c->h_icount, c->d_icount, cnt2.size() * sizeof(long long), hipMemcpyDeviceToHost, c->st));
             energy_tables();
             lap("tables");
@@ -708,7 +725,7 @@ static int seq_setup(ccj_ctx *c) {
         // the first item of every split, through pinned staging so the upload is asynchronous on st
         // (the fill's first launches follow it)
         const size_t nsp = (size_t)nb * KI_SPLIT;
-        if (!c->h_ioff) HIPCHK(cp, hipHostMalloc(&c->h_ioff, nsp * sizeof(long long), hipHostMallocDefault));
+        if (!c->h_ioff) HIPCHK(cp, hipHostMalloc(&c->h_ioff, (size_t)c->cap_ext[LX_ICOUNT] * sizeof(long long), hipHostMallocDefault));
         for (int b = 0; b < nb; ++b) {
             long long o = c->it_off[b];
             for (int s = 0; s < KI_SPLIT; ++s) {
@@ -729,9 +746,238 @@ static int seq_setup(ccj_ctx *c) {
     return CCJ_OK;
 }
 
-static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::unique_ptr<ccj_ctx> &c, ccj_ctx **out) {
+// --------------------------------------------------------------------------------------------
+// The layout of one sequence length: every quantity the device buffers' sizes and offsets derive
+// from n (with the d4 slot count and the split target).  create_impl sizes every allocation from
+// the extents of its capacity (layout_extents, exported as ccj_layout_extents); bind_layout lays a
+// length n <= capacity out inside them.
+// --------------------------------------------------------------------------------------------
+struct Layout {
+    int n = 0, nlev = 0, g_lo = 0, g_hi = 0;
+    int64_t total4 = 0, ncell = 0;      // elements of d4, cells per matrix
+    long long nx = 0, npm = 0, xpad = 0, xspan = 0, ppspan = 0, accC = 0, nlord = 0;
+    std::vector<LevelDesc> lv;          // base unset
+    std::vector<int64_t> off, offh;     // level offsets in d4 / in the host mirror
+    std::vector<LvlX> ldx;
+};
+
+static void layout_build(int n, int nm4, int split_target, bool share, Layout &L) {
+    const int nent = std::max(n, 1);
+    L = Layout{};
+    L.n = n;
+    L.lv.assign(nent, LevelDesc{nullptr, 0, 0, 0, 0});
+    L.off.assign(nent, 0);
+    L.offh.assign(nent, 0);
+    L.ldx.assign(nent, LvlX{0, 0});
+    int64_t off = 0, cells = 0;
+    for (int t = 0; t < n; ++t) {
+        const int m = n - t - 2;
+        LevelDesc D{nullptr, 0, 0, m > 0 ? m : 0, 0};
+        if (m > 0) {
+            long long C = 0;
+            ccj_level_layout(n, t, 1, &C, &D.M);
+            D.C = (int)C;
+            L.nlev = t + 1;
+        }
+        L.off[t] = off;
+        L.offh[t] = (int64_t)NMAT4 * cells;
+        L.lv[t] = D;
+        off += (int64_t)nm4 * D.C;
+        cells += D.C;
+    }
+    L.total4 = off;
+    L.ncell = cells;
+    // k_ppush addresses the PK rows of PPUSH_S consecutive levels as 32-bit byte offsets from the
+    // lowest one's start (one buffer resource per wave): that span must stay below 4 GB
+    for (int t = 0; t < L.nlev; ++t) {
+        const int tt = std::min(t + PPUSH_S - 1, L.nlev - 1);
+        L.ppspan = std::max<long long>(L.ppspan, 2 * (L.off[tt] + (long long)L.lv[tt].C - L.off[t]));
+    }
+    // interior-loop copies (ccj_engine.h): PLx+PRx mirror the level sizes, PMx is padded per (h, j).
+    // In front of every level: xpad sentinel elements of 32767, the null target of k_iloop's
+    // waves (a wave addresses its source levels as 32-bit offsets from the pad of the lowest)
+    L.xpad = n + 256;
+    long long ox = 0, op = 0;
+    for (int t = 0; t < L.nlev; ++t) {
+        ox += L.xpad;
+        op += L.xpad;
+        L.ldx[t] = LvlX{ox, op};
+        ox += 2LL * L.lv[t].C;
+        op += (long long)L.lv[t].m * n * (t + 1);
+        const int tlo = std::max(0, t - (2 * MAXLOOP - 2));  // a wave of level t + 3 .. t + 58 reads down to tlo
+        L.xspan = std::max({L.xspan, 2 * (ox - (L.ldx[tlo].lbx - L.xpad)), 2 * (op - (L.ldx[tlo].pmb - L.xpad))});
+    }
+    L.nx = ox;
+    L.npm = op;
+    // split-point sharing: the level range it covers (every level of it runs unsplit, so each leader
+    // and its followers run one cell per lane; sched_share_range, ccj_engine.h), the partial-record
+    // ring's slot size and the a-blocks k_level4d_lead runs (whatever the world: each block has one owner)
+    sched_share_range(n, split_target, share, L.g_lo, L.g_hi);
+    for (int t = L.g_lo; t < L.g_hi; ++t) {
+        L.accC = std::max<long long>(L.accC, L.lv[t].C);
+        for (int a = 0; a <= t; ++a) L.nlord += sched_lead_block(t, a, L.g_lo, nullptr);
+    }
+}
+
+static void layout_extents_of(const Layout &L, int G, long long *e) {
+    const long long n = L.n, plane = (n + 1) * (n + 2);
+    const bool sharing = L.g_hi > L.g_lo;
+    e[LX_D4] = L.total4;
+    e[LX_REC] = e[LX_RK] = e[LX_RL] = L.ncell;
+    e[LX_ACC] = sharing ? (long long)SHARE_SLOTS * SHARE_NACC * L.accC : 0;
+    e[LX_D4X] = L.nx + 2 * X_EDGE;
+    e[LX_PMX] = L.npm + 2 * X_EDGE;
+    e[LX_LORD] = L.nlord;
+    e[LX_LORD_OFF] = sharing ? n * G + 1 : 0;
+    e[LX_PLANE] = plane;
+    e[LX_IL] = plane * IL_CAP;
+    e[LX_ILSEG] = plane * IL_SEG;
+    e[LX_LEVELS] = std::max<long long>(n, 1);
+    e[LX_LXTAB] = 2 * n + 128;
+    e[LX_EVENTS] = n + 1;
+    e[LX_ICOUNT] = n * G * KI_SPLIT;
+    e[LX_PPUSH_SPAN] = L.ppspan;
+    e[LX_ILOOP_SPAN] = L.xspan;
+}
+
+// what a binding of n uses, or (as_capacity) what a context for every length 1 .. n allocates: the
+// entrywise maximum over those lengths (the sharing range, and with it the leader list and the
+// ring, moves with n and the split target, so those are not monotone in n)
+static std::vector<long long> layout_extents(int n, int G, int nm4, int split_target, bool share, bool as_capacity) {
+    std::vector<long long> e(LX_N, 0), x(LX_N, 0);
+    Layout L;
+    for (int q = as_capacity ? 1 : n; q <= n; ++q) {
+        layout_build(q, nm4, split_target, share, L);
+        layout_extents_of(L, G, x.data());
+        for (int k = 0; k < LX_N; ++k) e[k] = std::max(e[k], x[k]);
+    }
+    return e;
+}
+
+extern "C" const char *ccj_layout_extent_names(void) { return LX_NAMES; }
+
+extern "C" int ccj_layout_extents(int n, int split_target, int share, int full4, int as_capacity, long long *out, int cap) {
+    if (n < 1 || n > 1023 || split_target < 0 || (cap > 0 && !out)) return -CCJ_E_ARG;
+    if (cap >= LX_N) {
+        const std::vector<long long> e = layout_extents(n, 1, full4 ? NMAT4 : NMAT_D4, split_target, share != 0, as_capacity != 0);
+        std::copy(e.begin(), e.end(), out);
+    }
+    return LX_N;
+}
+
+static int span_check(ccj_ctx *c, const long long *e, int n) {
+    if (e[LX_PPUSH_SPAN] >= (1LL << 32))
+        return set_err(c, CCJ_E_ARG, "n=%d: the PK rows of %d levels exceed 4 GB (k_ppush offsets)", n, PPUSH_S);
+    if (e[LX_ILOOP_SPAN] >= (1LL << 32) - 4096)
+        return set_err(c, CCJ_E_ARG, "n=%d: the interior-loop copies of 56 levels exceed 4 GB (k_iloop offsets)", n);
+    return CCJ_OK;
+}
+
+// Bind the context to sequence length n <= its capacity: the host's level tables, the DevTables
+// fields and, on the context's stream, the device state that depends on n alone (k_bind_layout:
+// the level descriptors and the sentinels of the interior-loop copies; the leader lists, which
+// need the host's cost sort, through pinned staging).  No allocation, no blocking copy and no wait
+// on the stream: like seq_setup, a rebind never waits behind another context's fill.
+static int bind_layout(ccj_ctx *c, int n) {
+    if (n < 1 || n > c->ncap) return set_err(c, CCJ_E_ARG, "length %d outside the context's capacity 1..%d", n, c->ncap);
+    const int G = c->world;
+    Layout L;
+    layout_build(n, c->nm4, c->split_target, c->share, L);
+    if ((uint64_t)L.ncell != (uint64_t)ccj_num_cells(n)) return set_err(c, CCJ_E_ARG, "layout size mismatch");
+    long long e[LX_N];
+    layout_extents_of(L, G, e);
+    if (const int rc = span_check(c, e, n)) return rc;
+    for (int k = 0; k < LX_N; ++k)
+        if (e[k] > c->cap_ext[k]) return set_err(c, CCJ_E_ARG, "n=%d: layout extent %d exceeds the capacity's", n, k);
+    const bool sharing = L.g_hi > L.g_lo;
+    const bool relayout = n != c->n;
+    // the a-blocks k_level4d_lead runs on each sharing level (a leader or a full scan on either
+    // side; the roles of level4d_body), ordered by scan cost, longest first, so the longest
+    // waves do not start last.  A leader step costs about 2.5 plain steps.  One list per
+    // (level t, rank r) at t*world + r: the rank's own blocks (ccj_engine.h shard_owner).
+    c->lord_off.clear();
+    if (sharing) {
+        HIPCHK(c, hipEventSynchronize(c->ev_bind));  // the previous upload has read the staging
+        int *h_off = (int *)c->h_bind;
+        int16_t *h_lord = (int16_t *)(h_off + c->cap_ext[LX_LORD_OFF]);
+        c->lord_off.assign((size_t)n * G + 1, 0);
+        std::vector<std::pair<double, int>> blk;
+        int cnt = 0;
+        for (int tr = 0; tr < n * G; ++tr) {
+            const int t = tr / G, r = tr % G;
+            c->lord_off[tr] = cnt;
+            if (t < L.g_lo || t >= L.g_hi) continue;
+            blk.clear();
+            for (int a = 0; a <= t; ++a) {
+                double cost = 0;
+                if (shard_owner(a, G) != r || !sched_lead_block(t, a, L.g_lo, &cost)) continue;
+                blk.push_back({cost, a});
+            }
+            std::stable_sort(blk.begin(), blk.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
+            if (cnt + (long long)blk.size() > L.nlord) return set_err(c, CCJ_E_STATE, "leader list longer than its extent");
+            for (auto &b : blk) h_lord[cnt++] = (int16_t)b.second;
+        }
+        c->lord_off[(size_t)n * G] = cnt;
+        std::copy(c->lord_off.begin(), c->lord_off.end(), h_off);
+        if (cnt > 0) HIPCHK(c, hipMemcpyAsync(c->d_lord, h_lord, (size_t)cnt * sizeof(int16_t), hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipMemcpyAsync(c->d_lord_off, h_off, c->lord_off.size() * sizeof(int), hipMemcpyHostToDevice, c->st));
+        HIPCHK(c, hipEventRecord(c->ev_bind, c->st));
+    }
+    c->n = n;
+    c->rs = n + 2;
+    c->nlev = L.nlev;
+    c->lv_host.swap(L.lv);
+    c->lv_off.swap(L.off);
+    c->lv_offh.swap(L.offh);
+    c->total4 = L.total4;
+    c->ncell = L.ncell;
+    c->nrec = L.ncell;
+    c->nx = L.nx;
+    c->npm = L.npm;
+    c->xpad = L.xpad;
+    c->xspan = L.xspan;
+    for (int t = 0; t < n; ++t) c->lv_host[t].base = c->d4 ? c->d4 + c->lv_off[t] : nullptr;
+    const size_t plane = (size_t)(n + 1) * c->rs;
+    c->h2i.assign(A2_N * plane, 0);
+    c->hvt.assign(plane, 0);
+
+    DevTables &T = c->T;
+    T.n = n;
+    T.nlev = c->nlev;
+    T.rs = c->rs;
+    T.V = c->d2i + A2_V * plane;
+    T.WM = c->d2i + A2_WM * plane;
+    T.WMv = c->d2i + A2_WMV * plane;
+    T.WMp = c->d2i + A2_WMP * plane;
+    T.P = c->d2i + A2_P * plane;
+    T.WBP = c->d2i + A2_WBP * plane;
+    T.WPP = c->d2i + A2_WPP * plane;
+    T.WB = c->d2i + A2_WB * plane;
+    T.WP = c->d2i + A2_WP * plane;
+    T.tabN = (long long)plane;
+    T.nrec = c->nrec;
+    T.nx = c->nx;
+    T.npm = c->npm;
+    T.xpad = c->xpad;
+    T.xspan = c->xspan;
+    T.g_lo = L.g_lo;
+    T.g_hi = L.g_hi;
+    T.acc = sharing ? c->d_acc : nullptr;
+    T.lord = sharing ? c->d_lord : nullptr;
+    T.lord_off = sharing ? c->d_lord_off : nullptr;
+    T.lord_off_h = c->lord_off.empty() ? nullptr : c->lord_off.data();
+    T.accC = L.accC;
+    // a changed layout moves every level of the interior-loop copies: 32767 again over the bound
+    // extent, never over the capacity's
+    const bool fill = relayout;
+    HIPCHK(c, (hipError_t)ccjk_bind_layout(&T, (int)c->lv_host.size(), c->nm4, c->d_lv, c->d_lb, c->d_ld, c->d_ldx, c->d4x_alloc,
+                                           fill ? e[LX_D4X] : 0, c->pmx_alloc, fill ? e[LX_PMX] : 0, c->st));
+    return CCJ_OK;
+}
+
+static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nmax, std::unique_ptr<ccj_ctx> &c, ccj_ctx **out) {
     c->seq = prob->seq;
-    c->n = (int)c->seq.size();
+    const int n = (int)c->seq.size();
     c->dangles = prob->dangles;
     c->noGU = prob->noGU ? 1 : 0;
     c->device = opts ? opts->device : 0;
@@ -762,10 +1008,15 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     c->pen = Penalties{pk.PS, pk.PSM, pk.PSP, pk.PB, pk.PUP, pk.PPS, pk.a, pk.b, pk.c, pk.ap, pk.bp, pk.cp};
     c->e_stP = pk.e_stP;
     c->e_intP = pk.e_intP;
-    const int n = c->n;
     if (n < 1) return CCJ_E_ARG;
+    if (nmax < n) return set_err(c.get(), CCJ_E_ARG, "ccj_create_cap: sequence of length %d exceeds the capacity %d", n, nmax);
     for (char ch : c->seq)
         if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'U' || ch == 'T')) return CCJ_E_ARG;
+    if (nmax > 1023) return set_err(c.get(), CCJ_E_ARG, "sequence longer than 1023 (k_iloop item encoding)");
+    if (c->world > 1 && nmax != n)
+        return set_err(c.get(), CCJ_E_ARG, "ccj_create_cap: a band-sharded context holds one length (capacity %d, sequence %d)",
+                       nmax, n);
+    c->ncap = nmax;
 
     // pair_mat.h:81-155 make_pair_matrix + 159-183 encode_sequence
     const int base_rtype[8] = {0, 2, 1, 4, 3, 6, 5, 7};
@@ -775,47 +1026,20 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     if (c->noGU) c->pair[3][4] = c->pair[4][3] = 0;
     for (int x = 0; x < 8; ++x)
         for (int y = 0; y < 8; ++y) c->rtype[c->pair[x][y]] = c->pair[y][x];
-    // (int)(lxc*log(x/30.)) with the host libm, as ViennaRNA computes it
-    c->lx.assign(2 * n + 128, 0);
-    for (size_t x = 31; x < c->lx.size(); ++x) c->lx[x] = (int)(c->prm.lxc * log((double)x / 30.));
-    c->rs = n + 2;
 
-    // level layout.  d4 has the NMAT_D4 slots per level the fill writes, or all 22 (a full context)
+    // d4 has the NMAT_D4 slots per level the fill writes, or all 22 (a full context)
     // where the band-sharded exchange packs them or a host mirror streams them during the fill
     // (ccj_engine.h carrier); CCJ_D4_FULL=1 makes any context full (A/B timing).  The host mirror
     // always has 22
     c->full4 = (c->world > 1 && !c->simulate) || c->overlap || (getenv("CCJ_D4_FULL") && atoi(getenv("CCJ_D4_FULL")) != 0);
     c->nm4 = c->full4 ? NMAT4 : NMAT_D4;
-    c->lv_host.assign(std::max(n, 1), LevelDesc{nullptr, 0, 0, 0, 0});
-    c->lv_off.assign(std::max(n, 1), 0);
-    c->lv_offh.assign(std::max(n, 1), 0);
-    int64_t off = 0, cells = 0;
-    for (int t = 0; t < n; ++t) {
-        const int m = n - t - 2;
-        LevelDesc L{nullptr, 0, 0, m > 0 ? m : 0, 0};
-        if (m > 0) {
-            long long C = 0;
-            ccj_level_layout(n, t, c->world, &C, &L.M);
-            L.C = (int)C;
-            c->nlev = t + 1;
-        }
-        c->lv_off[t] = off;
-        c->lv_offh[t] = (int64_t)NMAT4 * cells;
-        c->lv_host[t] = L;
-        off += (int64_t)c->nm4 * L.C;
-        cells += L.C;
-    }
-    c->total4 = off;
-    c->ncell = cells;
-    if ((uint64_t)cells != (uint64_t)ccj_num_cells(n))
-        return set_err(c.get(), CCJ_E_ARG, "layout size mismatch");
-    // k_ppush addresses the PK rows of PPUSH_S consecutive levels as 32-bit byte offsets from the
-    // lowest one's start (one buffer resource per wave): that span must stay below 4 GB
-    for (int t = 0; t < c->nlev; ++t) {
-        const int tt = std::min(t + PPUSH_S - 1, c->nlev - 1);
-        if (2 * (c->lv_off[tt] + (long long)c->lv_host[tt].C - c->lv_off[t]) >= (1LL << 32))
-            return set_err(c.get(), CCJ_E_ARG, "n=%d: the PK rows of %d levels exceed 4 GB (k_ppush offsets)", n, PPUSH_S);
-    }
+    // every allocation below is sized from the capacity's extents and nothing else
+    c->cap_ext = layout_extents(nmax, c->world, c->nm4, c->split_target, c->share, true);
+    const std::vector<long long> &X = c->cap_ext;
+    if (const int rc = span_check(c.get(), X.data(), nmax)) return rc;
+    // (int)(lxc*log(x/30.)) with the host libm, as ViennaRNA computes it
+    c->lx.assign((size_t)X[LX_LXTAB], 0);
+    for (size_t x = 31; x < c->lx.size(); ++x) c->lx[x] = (int)(c->prm.lxc * log((double)x / 30.));
 
     ccj_ctx *cp = c.get();
     HIPCHK(cp, hipSetDevice(c->device));
@@ -830,79 +1054,48 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     // ev_start / ev_end, which the host waits on, keep it.
     constexpr unsigned fence_fl = (unsigned)hipEventDisableSystemFence;
     const unsigned sync_fl = hipEventDisableTiming | fence_fl;
-    c->il_done.resize(n + 1);
+    const size_t nev = (size_t)X[LX_EVENTS];
+    c->il_done.resize(nev);
     for (auto &e : c->il_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->dg_done.resize(n + 1);
+    c->dg_done.resize(nev);
     for (auto &e : c->dg_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
     HIPCHK(cp, hipEventCreate(&c->ev_start));
     HIPCHK(cp, hipEventCreate(&c->ev_end));
     HIPCHK(cp, hipEventCreate(&c->ev_pre));
-    c->lev_done.resize(n + 1);
+    c->lev_done.resize(nev);
     // timed: the level durations (mode 1; recording them untimed measured the same)
     for (auto &e : c->lev_done) HIPCHK(cp, hipEventCreateWithFlags(&e, fence_fl));
-    c->p_done.resize(n + 1);
+    c->p_done.resize(nev);
     for (auto &e : c->p_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->pp_done.resize(n + 1);
+    c->pp_done.resize(nev);
     for (auto &e : c->pp_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->bulk_done.resize(n + 1);
+    c->bulk_done.resize(nev);
     for (auto &e : c->bulk_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
     HIPCHK(cp, hipEventCreateWithFlags(&c->ev_bpacked, sync_fl));
     HIPCHK(cp, hipEventCreateWithFlags(&c->ev_bcopied, sync_fl));
-    c->tev.resize(TEV_PER * (size_t)n + TEV_PER);
+    c->tev.resize(TEV_PER * nev);
     for (auto &e : c->tev) HIPCHK(cp, hipEventCreate(&e));
 
-    const size_t plane = (size_t)(n + 1) * c->rs;
-    const size_t ie_elems = (size_t)(n + 1) * c->rs;  // the u1 = u2 = 0 plane (k_build_il evaluates the rest)
-    if (c->total4 > 0 && hipMalloc(&c->d4, (size_t)c->total4 * sizeof(int16_t)) != hipSuccess)
-        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for 4-D matrices failed", c->total4 * 2e-9);
+    const size_t plane = (size_t)X[LX_PLANE];
+    if (X[LX_D4] > 0 && hipMalloc(&c->d4, (size_t)X[LX_D4] * sizeof(int16_t)) != hipSuccess)
+        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for 4-D matrices failed", X[LX_D4] * 2e-9);
     // loop records: one RA (8 bytes), RK (8) and RL (4) record per cell, each its own array (ccj_engine.h)
-    c->nrec = c->ncell;
-    if (c->nrec > 0 && (hipMalloc(&c->d_rec, (size_t)c->nrec * sizeof(rec_t)) != hipSuccess ||
-                        hipMalloc(&c->d_rk, (size_t)c->nrec * sizeof(rk_t)) != hipSuccess ||
-                        hipMalloc(&c->d_rl, (size_t)c->nrec * sizeof(rl_t)) != hipSuccess))
-        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for loop records failed", c->nrec * (REC_BYTES * 1e-9));
-    // split-point sharing: the level range it covers (every level of it runs unsplit, so each leader
-    // and its followers run one cell per lane) and the partial-record ring
-    int g_lo = 0, g_hi = 0;
-    long long accC = 0;
-    // from the first level that runs unsplit to the last level (sched_share_range, ccj_engine.h)
-    sched_share_range(n, c->split_target, c->share, g_lo, g_hi);
-    for (int t = g_lo; t < g_hi; ++t) accC = std::max<long long>(accC, c->lv_host[t].C);
-    if (g_hi > g_lo) {
-        // the a-blocks k_level4d_lead runs on each sharing level (a leader or a full scan on either
-        // side; the roles of level4d_body), ordered by scan cost, longest first, so the longest
-        // waves do not start last.  A leader step costs about 2.5 plain steps.  One list per
-        // (level t, rank r) at t*world + r: the rank's own blocks (ccj_engine.h shard_owner).
-        std::vector<int16_t> lord;
-        const int G = c->world;
-        c->lord_off.assign((size_t)n * G + 1, 0);
-        std::vector<std::pair<double, int>> blk;
-        for (int tr = 0; tr < n * G; ++tr) {
-            const int t = tr / G, r = tr % G;
-            c->lord_off[tr] = (int)lord.size();
-            if (t < g_lo || t >= g_hi) continue;
-            blk.clear();
-            for (int a = 0; a <= t; ++a) {
-                double cost = 0;
-                if (shard_owner(a, G) != r || !sched_lead_block(t, a, g_lo, &cost)) continue;
-                blk.push_back({cost, a});
-            }
-            std::stable_sort(blk.begin(), blk.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
-            for (auto &e : blk) lord.push_back((int16_t)e.second);
-        }
-        c->lord_off[(size_t)n * G] = (int)lord.size();
-        HIPCHK(cp, hipMalloc(&c->d_lord, std::max<size_t>(lord.size(), 1) * sizeof(int16_t)));
-        HIPCHK(cp, hipMalloc(&c->d_lord_off, c->lord_off.size() * sizeof(int)));
-        if (!lord.empty())
-            HIPCHK(cp, hipMemcpy(c->d_lord, lord.data(), lord.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-        HIPCHK(cp, hipMemcpy(c->d_lord_off, c->lord_off.data(), c->lord_off.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (X[LX_REC] > 0 && (hipMalloc(&c->d_rec, (size_t)X[LX_REC] * sizeof(rec_t)) != hipSuccess ||
+                          hipMalloc(&c->d_rk, (size_t)X[LX_RK] * sizeof(rk_t)) != hipSuccess ||
+                          hipMalloc(&c->d_rl, (size_t)X[LX_RL] * sizeof(rl_t)) != hipSuccess))
+        return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for loop records failed", X[LX_REC] * (REC_BYTES * 1e-9));
+    // split-point sharing (where some length up to the capacity shares): the leader lists with
+    // their pinned staging, and the partial-record ring
+    if (X[LX_LORD_OFF] > 0) {
+        HIPCHK(cp, hipMalloc(&c->d_lord, std::max<size_t>((size_t)X[LX_LORD], 1) * sizeof(int16_t)));
+        HIPCHK(cp, hipMalloc(&c->d_lord_off, (size_t)X[LX_LORD_OFF] * sizeof(int)));
+        if (hipMalloc(&c->d_acc, (size_t)X[LX_ACC] * sizeof(uint2)) != hipSuccess)
+            return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for split-sharing records failed", X[LX_ACC] * 8e-9);
+        HIPCHK(cp, hipHostMalloc(&c->h_bind, (size_t)X[LX_LORD_OFF] * sizeof(int) + (size_t)X[LX_LORD] * sizeof(int16_t),
+                                 hipHostMallocDefault));
+        HIPCHK(cp, hipEventCreateWithFlags(&c->ev_bind, hipEventDisableTiming));
     }
-    if (g_hi > g_lo) {
-        if (hipMalloc(&c->d_acc, (size_t)SHARE_SLOTS * SHARE_NACC * accC * sizeof(uint2)) != hipSuccess)
-            return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for split-sharing records failed",
-                           SHARE_SLOTS * SHARE_NACC * accC * 8e-9);
-    }
-    HIPCHK(cp, hipMalloc(&c->d_ie, ie_elems * sizeof(int16_t)));
+    HIPCHK(cp, hipMalloc(&c->d_ie, plane * sizeof(int16_t)));  // the u1 = u2 = 0 plane (k_build_il evaluates the rest)
     HIPCHK(cp, hipMalloc(&c->d_est, plane * sizeof(int16_t)));
     HIPCHK(cp, hipMalloc(&c->d_hp, plane * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_pt, plane));
@@ -910,57 +1103,33 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     HIPCHK(cp, hipMalloc(&c->d_rtype, 8));
     HIPCHK(cp, hipMalloc(&c->d_lx, c->lx.size() * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_err, sizeof(int)));
-    HIPCHK(cp, hipMalloc(&c->d_S, (n + 2) * sizeof(short)));
-    HIPCHK(cp, hipMalloc(&c->d_S1, (n + 2) * sizeof(short)));
+    HIPCHK(cp, hipMalloc(&c->d_S, (nmax + 2) * sizeof(short)));
+    HIPCHK(cp, hipMalloc(&c->d_S1, (nmax + 2) * sizeof(short)));
     HIPCHK(cp, hipMalloc(&c->d_prm, sizeof(ccj_energy_params)));
-    HIPCHK(cp, hipMalloc(&c->d_lv, c->lv_host.size() * sizeof(LevelDesc)));
-    HIPCHK(cp, hipMalloc(&c->d_lb, c->lv_off.size() * sizeof(long long)));
-    HIPCHK(cp, hipMalloc(&c->d_ld, c->lv_off.size() * sizeof(LvlDev)));
+    const size_t nent = (size_t)X[LX_LEVELS];
+    HIPCHK(cp, hipMalloc(&c->d_lv, nent * sizeof(LevelDesc)));
+    HIPCHK(cp, hipMalloc(&c->d_lb, nent * sizeof(long long)));
+    HIPCHK(cp, hipMalloc(&c->d_ld, nent * sizeof(LvlDev)));
     {
-        // interior-loop copies (ccj_engine.h): PLx+PRx mirror the level sizes, PMx is padded per (h, j).
-        // In front of every level: xpad sentinel elements of 32767, the null target of k_iloop's
-        // waves (a wave addresses its source levels as 32-bit offsets from the pad of the lowest)
-        const long long xpad = n + 256;
-        std::vector<LvlX> ldx(c->lv_off.size(), LvlX{0, 0});
-        long long ox = 0, op = 0, span = 0;
-        for (int t = 0; t < c->nlev; ++t) {
-            ox += xpad;
-            op += xpad;
-            ldx[t] = LvlX{ox, op};
-            ox += 2LL * c->lv_host[t].C;
-            op += (long long)c->lv_host[t].m * n * (t + 1);
-            const int tlo = std::max(0, t - (2 * MAXLOOP - 2));  // a wave of level t + 3 .. t + 58 reads down to tlo
-            span = std::max({span, 2 * (ox - (ldx[tlo].lbx - xpad)), 2 * (op - (ldx[tlo].pmb - xpad))});
-        }
-        if (span >= (1LL << 32) - 4096)
-            return set_err(cp, CCJ_E_ARG, "n=%d: the interior-loop copies of 56 levels exceed 4 GB (k_iloop offsets)", n);
-        const size_t pad = 256;
-        c->nx = ox;
-        c->npm = op;
-        c->xpad = xpad;
-        c->xspan = span;
-        // pad elements on both sides; everything starts as 32767 (the pads stay so: no level writes them)
-        if (hipMalloc(&c->d4x_alloc, ((size_t)ox + 2 * pad) * sizeof(int16_t)) != hipSuccess ||
-            hipMalloc(&c->pmx_alloc, ((size_t)op + 2 * pad) * sizeof(int16_t)) != hipSuccess)
-            return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for interior-loop copies failed", (ox + op) * 2e-9);
-        HIPCHK(cp, hipMemsetD16((hipDeviceptr_t)c->d4x_alloc, (unsigned short)INTERN_INF, (size_t)ox + 2 * pad));
-        HIPCHK(cp, hipMemsetD16((hipDeviceptr_t)c->pmx_alloc, (unsigned short)INTERN_INF, (size_t)op + 2 * pad));
-        c->d4x = c->d4x_alloc + pad;
-        c->pmx = c->pmx_alloc + pad;
-        HIPCHK(cp, hipMalloc(&c->d_ldx, ldx.size() * sizeof(LvlX)));
-        HIPCHK(cp, hipMemcpy(c->d_ldx, ldx.data(), ldx.size() * sizeof(LvlX), hipMemcpyHostToDevice));
-        std::vector<int16_t> dummy((size_t)n + 64, (int16_t)INTERN_INF);
+        // interior-loop copies: X_EDGE pad elements on both sides; bind_layout (k_bind_layout) sets the
+        // bound extent to 32767 (the pads stay so: no level writes them)
+        if (hipMalloc(&c->d4x_alloc, (size_t)X[LX_D4X] * sizeof(int16_t)) != hipSuccess ||
+            hipMalloc(&c->pmx_alloc, (size_t)X[LX_PMX] * sizeof(int16_t)) != hipSuccess)
+            return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for interior-loop copies failed",
+                           (X[LX_D4X] + X[LX_PMX]) * 2e-9);
+        c->d4x = c->d4x_alloc + X_EDGE;
+        c->pmx = c->pmx_alloc + X_EDGE;
+        HIPCHK(cp, hipMalloc(&c->d_ldx, nent * sizeof(LvlX)));
+        std::vector<int16_t> dummy((size_t)nmax + 64, (int16_t)INTERN_INF);
         HIPCHK(cp, hipMalloc(&c->d_dummy, dummy.size() * sizeof(int16_t)));
         HIPCHK(cp, hipMemcpy(c->d_dummy, dummy.data(), dummy.size() * sizeof(int16_t), hipMemcpyHostToDevice));
         {  // the k_iloop work items' candidate lists (k_build_il)
-            const size_t pairs = (size_t)(n + 1) * c->rs;
-            const size_t ents = pairs * IL_CAP;
-            HIPCHK(cp, hipMalloc(&c->d_il, ents * sizeof(uint2)));
-            HIPCHK(cp, hipMalloc(&c->d_ilm, ents * sizeof(uint2)));
-            HIPCHK(cp, hipMalloc(&c->d_ilseg, pairs * IL_SEG * sizeof(uint32_t)));
-            HIPCHK(cp, hipMalloc(&c->d_ilmseg, pairs * IL_SEG * sizeof(uint32_t)));
-            HIPCHK(cp, hipMemset(c->d_ilseg, 0, pairs * IL_SEG * sizeof(uint32_t)));
-            HIPCHK(cp, hipMemset(c->d_ilmseg, 0, pairs * IL_SEG * sizeof(uint32_t)));
+            HIPCHK(cp, hipMalloc(&c->d_il, (size_t)X[LX_IL] * sizeof(uint2)));
+            HIPCHK(cp, hipMalloc(&c->d_ilm, (size_t)X[LX_IL] * sizeof(uint2)));
+            HIPCHK(cp, hipMalloc(&c->d_ilseg, (size_t)X[LX_ILSEG] * sizeof(uint32_t)));
+            HIPCHK(cp, hipMalloc(&c->d_ilmseg, (size_t)X[LX_ILSEG] * sizeof(uint32_t)));
+            HIPCHK(cp, hipMemset(c->d_ilseg, 0, (size_t)X[LX_ILSEG] * sizeof(uint32_t)));
+            HIPCHK(cp, hipMemset(c->d_ilmseg, 0, (size_t)X[LX_ILSEG] * sizeof(uint32_t)));
         }
     }
     HIPCHK(cp, hipMalloc(&c->d2i, A2_N * plane * sizeof(int)));
@@ -968,21 +1137,17 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     HIPCHK(cp, hipMalloc(&c->d_tab, 6 * plane * sizeof(int16_t)));  // k_init2d resets them with every fill
     HIPCHK(cp, hipMalloc(&c->d_cf, NCF * plane * sizeof(int)));     // and these
     HIPCHK(cp, hipMalloc(&c->d_pk, plane * sizeof(unsigned long long)));
-    HIPCHK(cp, hipMalloc(&c->d_W, (n + 1) * sizeof(int)));
+    HIPCHK(cp, hipMalloc(&c->d_W, (nmax + 1) * sizeof(int)));
     HIPCHK(cp, hipMalloc(&c->d_wterm, plane * sizeof(int)));
-    HIPCHK(cp, hipMalloc(&c->d_fpair, (n + 1) * sizeof(int)));
-    HIPCHK(cp, hipMalloc(&c->d_ftype, (n + 1)));
+    HIPCHK(cp, hipMalloc(&c->d_fpair, (nmax + 1) * sizeof(int)));
+    HIPCHK(cp, hipMalloc(&c->d_ftype, (nmax + 1)));
     HIPCHK(cp, hipMalloc(&c->d_btout, sizeof(BtOut)));
     HIPCHK(cp, hipMalloc(&c->d_vt, plane));
     // the pinned host mirror is only needed by the host traceback and the getters: allocate it up
-    // front when the fill streams into it, else on first use (ccj_sync_host)
-    if (c->overlap && c->total4 > 0 &&
-        hipHostMalloc(&c->h4, (size_t)NMAT4 * c->ncell * sizeof(int16_t), hipHostMallocDefault) != hipSuccess)
-        return set_err(cp, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", NMAT4 * c->ncell * 2e-9);
-    c->h2i.assign(A2_N * plane, 0);
-    c->hvt.assign(plane, 0);
-
-    for (int t = 0; t < n; ++t) c->lv_host[t].base = c->d4 ? c->d4 + c->lv_off[t] : nullptr;
+    // front when the fill streams into it, else on first use (ccj_sync_host); sized for the capacity
+    if (c->overlap && X[LX_REC] > 0 &&
+        hipHostMalloc(&c->h4, (size_t)NMAT4 * X[LX_REC] * sizeof(int16_t), hipHostMallocDefault) != hipSuccess)
+        return set_err(cp, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", NMAT4 * X[LX_REC] * 2e-9);
 
     int8_t pair8[64], rt8[8];
     for (int x = 0; x < 8; ++x) {
@@ -993,23 +1158,9 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     HIPCHK(cp, hipMemcpy(c->d_rtype, rt8, 8, hipMemcpyHostToDevice));
     HIPCHK(cp, hipMemcpy(c->d_lx, c->lx.data(), c->lx.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(cp, hipMemcpy(c->d_prm, &c->prm, sizeof(ccj_energy_params), hipMemcpyHostToDevice));
-    HIPCHK(cp, hipMemcpy(c->d_lv, c->lv_host.data(), c->lv_host.size() * sizeof(LevelDesc), hipMemcpyHostToDevice));
-    {
-        std::vector<long long> lb(c->lv_off.begin(), c->lv_off.end());
-        HIPCHK(cp, hipMemcpy(c->d_lb, lb.data(), lb.size() * sizeof(long long), hipMemcpyHostToDevice));
-        std::vector<LvlDev> ld(c->lv_off.size());
-        long long lr = 0;
-        for (size_t t = 0; t < ld.size(); ++t) {
-            ld[t] = LvlDev{c->lv_off[t], lr, c->lv_host[t].C, c->lv_host[t].M, {0, 0}};
-            lr += (long long)c->lv_host[t].C;
-        }
-        HIPCHK(cp, hipMemcpy(c->d_ld, ld.data(), ld.size() * sizeof(LvlDev), hipMemcpyHostToDevice));
-    }
 
+    // what no binding moves; bind_layout sets the rest
     DevTables &T = c->T;
-    T.n = n;
-    T.nlev = c->nlev;
-    T.rs = c->rs;
     T.dangles = c->dangles;
     T.pen = c->pen;
     T.e_stP = c->e_stP;
@@ -1024,16 +1175,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.hp = c->d_hp;
     T.est = c->d_est;
     T.ie = c->d_ie;
-    T.V = c->d2i + A2_V * plane;
-    T.WM = c->d2i + A2_WM * plane;
-    T.WMv = c->d2i + A2_WMV * plane;
-    T.WMp = c->d2i + A2_WMP * plane;
-    T.P = c->d2i + A2_P * plane;
     T.Pk = c->d_pk;
-    T.WBP = c->d2i + A2_WBP * plane;
-    T.WPP = c->d2i + A2_WPP * plane;
-    T.WB = c->d2i + A2_WB * plane;
-    T.WP = c->d2i + A2_WP * plane;
     T.WBW = c->d_wbw;
     T.Vt = c->d_vt;
     T.lv = c->d_lv;
@@ -1046,13 +1188,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.rl = c->d_rl;
     T.cf = c->d_cf;
     T.tab = c->d_tab;
-    T.tabN = (long long)plane;
-    T.nrec = c->nrec;
     T.pmx = c->pmx;
-    T.nx = c->nx;
-    T.npm = c->npm;
-    T.xpad = c->xpad;
-    T.xspan = c->xspan;
     T.ldx = c->d_ldx;
     T.il = c->d_il;
     T.ilm = c->d_ilm;
@@ -1063,27 +1199,32 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
     T.ilmseg = c->d_ilmseg;
     T.err = c->d_err;
     T.split_target = c->split_target;
-    T.g_lo = g_lo;
-    T.g_hi = g_hi;
-    T.acc = c->d_acc;
-    T.lord = c->d_lord;
-    T.lord_off = c->d_lord_off;
-    T.lord_off_h = c->lord_off.empty() ? nullptr : c->lord_off.data();
-    T.accC = accC;
     {
         const int G = c->world;
-        HIPCHK(cp, hipMalloc(&c->d_icount, (size_t)n * G * KI_SPLIT * sizeof(long long)));
-        HIPCHK(cp, hipMalloc(&c->d_ioff, (size_t)n * G * KI_SPLIT * sizeof(long long)));
+        HIPCHK(cp, hipMalloc(&c->d_icount, (size_t)X[LX_ICOUNT] * sizeof(long long)));
+        HIPCHK(cp, hipMalloc(&c->d_ioff, (size_t)X[LX_ICOUNT] * sizeof(long long)));
+        if (nmax > n) {
+            // a capacity context allocates its k_iloop work items once, for the most any sequence up
+            // to the capacity can have: every row of every level (ccj_items.h item_rows, which grow
+            // with n) in its most chunks
+            size_t bound = 1;
+            for (int t = 4; t < nmax - 2; ++t) {
+                const ItemRows R = item_rows(nmax, t, 1, 0);
+                bound += (size_t)(R.nPL + R.nPR + R.nPM) * (nmax / IL_CW + 1);
+            }
+            c->items_cap = bound;
+            HIPCHK(cp, hipMalloc(&c->d_items, c->items_cap * sizeof(uint32_t)));
+        }
         if (G > 1 && !c->simulate) {
             // exchange slices, per part: 22 matrices x the largest rank's blocks of the
-            // part x M, then the part's tail
+            // part x M, then the part's tail (a band-sharded context holds one length: nmax == n)
             for (int part = 0; part < 2; ++part) {
                 c->xnmax[part].assign(n, 0);
                 size_t slice = 0;
-                for (int t = 0; t < c->nlev; ++t) {
-                    const int nm = xch_nmax(t, G, part);
+                for (int t = 0; t + 2 < n; ++t) {
+                    const int nm = xch_nmax(t, G, part), m = n - t - 2;
                     c->xnmax[part][t] = nm;
-                    slice = std::max(slice, (size_t)xch_slice(n, nm, c->lv_host[t].M, part));
+                    slice = std::max(slice, (size_t)xch_slice(n, nm, m * (m + 1) / 2, part));
                 }
                 if (hipMalloc(&c->d_send[part], std::max<size_t>(slice, 1) * sizeof(int16_t)) != hipSuccess ||
                     hipMalloc(&c->d_recv[part], std::max<size_t>(slice * G, 1) * sizeof(int16_t)) != hipSuccess)
@@ -1092,12 +1233,14 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, std::un
             }
         }
     }
+    c->n = 0;  // no binding yet: bind_layout sets the sentinels of its layout
+    if (const int rc = bind_layout(cp, n)) return rc;
     if (const int rc = seq_setup(cp)) return rc;
     *out = c.release();
     return CCJ_OK;
 }
 
-extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_ctx **out) {
+extern "C" int ccj_create_cap(const ccj_problem *prob, const ccj_options *opts, int nmax, ccj_ctx **out) {
     if (!out) return CCJ_E_ARG;
     *out = nullptr;
     g_create_err.clear();
@@ -1106,7 +1249,7 @@ extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_
         return CCJ_E_ARG;
     }
     std::unique_ptr<ccj_ctx> c(new ccj_ctx());
-    const int rc = create_impl(prob, opts, c, out);
+    const int rc = create_impl(prob, opts, nmax, c, out);
     if (rc != CCJ_OK) {
         g_create_err = c ? c->err : std::string("ccj_create failed");
         if (g_create_err.empty()) g_create_err = "invalid problem (sequence alphabet, length or parameter blob)";
@@ -1115,24 +1258,43 @@ extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_
     return rc;
 }
 
-extern "C" int ccj_reset(ccj_ctx *c, const char *seq) {
+extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_ctx **out) {
+    return ccj_create_cap(prob, opts, prob && prob->seq ? (int)strlen(prob->seq) : 0, out);
+}
+
+// ccj_reset (same_length) and ccj_rebind: `what` names the call in the messages
+static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char *what) {
     if (!c || !seq) return CCJ_E_ARG;
     const std::string s(seq);
-    if ((int)s.size() != c->n) return set_err(c, CCJ_E_ARG, "ccj_reset: length %zu differs from the context's n=%d", s.size(), c->n);
+    const int len = (int)s.size();
+    if (same_length && len != c->n)
+        return set_err(c, CCJ_E_ARG, "%s: length %zu differs from the context's n=%d", what, s.size(), c->n);
+    if (len < 1 || len > c->ncap)
+        return set_err(c, CCJ_E_ARG, "%s: length %zu outside the context's capacity 1..%d", what, s.size(), c->ncap);
     for (char ch : s)
         if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'U' || ch == 'T'))
-            return set_err(c, CCJ_E_ARG, "ccj_reset: invalid character in sequence");
-    if (c->pending || c->res_pending) return set_err(c, CCJ_E_STATE, "ccj_reset: a fold is in flight (ccj_wait first)");
+            return set_err(c, CCJ_E_ARG, "%s: invalid character in sequence", what);
+    if (c->world > 1 && len != c->n)
+        return set_err(c, CCJ_E_ARG, "%s: a band-sharded context holds one length (n=%d)", what, c->n);
+    if (c->pending || c->res_pending) return set_err(c, CCJ_E_STATE, "%s: a fold is in flight (ccj_wait first)", what);
     HIPCHK(c, hipSetDevice(c->device));
     // no fold is in flight (checked above): ccj_wait / ccj_fill returned only after the fill and
     // the traceback completed, so the streams are idle.  Only the optional host-mirror copies can
     // still run.  (A hipStreamSynchronize here would enqueue a marker that can wait behind another
     // context's fill on a shared hardware queue.)
     if (c->overlap && c->h4) HIPCHK(c, hipStreamSynchronize(c->st_copy));
+    if (len != c->n) {
+        if (const int rc = bind_layout(c, len)) return rc;
+    }
     c->seq = s;
     c->W.clear();
     return seq_setup(c);
 }
+
+extern "C" int ccj_reset(ccj_ctx *c, const char *seq) { return rebind_impl(c, seq, true, "ccj_reset"); }
+extern "C" int ccj_rebind(ccj_ctx *c, const char *seq) { return rebind_impl(c, seq, false, "ccj_rebind"); }
+extern "C" int ccj_capacity(const ccj_ctx *c) { return c ? c->ncap : 0; }
+
 
 // Enqueue the whole fill on the context's streams; it ends with ev_end on st, after which every
 // stream's work of the fill is complete (st waits for the last span, which waits for the last P,
@@ -1525,8 +1687,9 @@ extern "C" int ccj_sync_host(ccj_ctx *c) {
         HIPCHK(c, hipStreamSynchronize(c->st_copy));
     } else if (c->total4 > 0) {
         const size_t hbytes = (size_t)NMAT4 * c->ncell * sizeof(int16_t);
-        if (!c->h4 && hipHostMalloc(&c->h4, hbytes, hipHostMallocDefault) != hipSuccess)
-            return set_err(c, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", hbytes * 1e-9);
+        const size_t cap_bytes = (size_t)NMAT4 * c->cap_ext[LX_REC] * sizeof(int16_t);  // once, for the capacity
+        if (!c->h4 && hipHostMalloc(&c->h4, cap_bytes, hipHostMallocDefault) != hipSuccess)
+            return set_err(c, CCJ_E_OOM, "pinned host allocation of %.2f GB failed", cap_bytes * 1e-9);
         if (c->full4) {  // d4 has the mirror's layout
             for (int t = 0; t < c->nlev; ++t) HIPCHK(c, (hipError_t)expand_tab_slots(c, t, c->st));
             HIPCHK(c, hipStreamSynchronize(c->st));
@@ -1593,9 +1756,9 @@ int result_enqueue(ccj_ctx *c) {
     const int n = c->n;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->hr_W) {
-        HIPCHK(c, hipHostMalloc(&c->hr_W, (n + 1) * sizeof(int), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(&c->hr_fp, (n + 1) * sizeof(int), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(&c->hr_ft, n + 1, hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc(&c->hr_W, (c->ncap + 1) * sizeof(int), hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc(&c->hr_fp, (c->ncap + 1) * sizeof(int), hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc(&c->hr_ft, c->ncap + 1, hipHostMallocDefault));
         HIPCHK(c, hipHostMalloc(&c->hr_bo, sizeof(BtOut), hipHostMallocDefault));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_res, hipEventDisableTiming));
     }
@@ -2169,6 +2332,8 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
         hipFree(c->d_recv[part]);
     }
     if (c->h_stage) hipHostFree(c->h_stage);
+    if (c->h_bind) hipHostFree(c->h_bind);
+    if (c->ev_bind) hipEventDestroy(c->ev_bind);
     if (c->h_ioff) hipHostFree(c->h_ioff);
     if (c->h_icount) hipHostFree(c->h_icount);
     if (c->ev_stage) hipEventDestroy(c->ev_stage);

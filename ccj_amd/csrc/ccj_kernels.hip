@@ -2234,6 +2234,79 @@ extern "C" int ccjk_canon(const DevTables *T, int x, const long long *offij, int
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Binding a context to a sequence length n <= its capacity (ccj_create_cap / ccj_rebind): the device
+// state that depends on n alone, rebuilt on the context's stream without a host copy.
+//   * Workgroup 0 writes the per-level descriptors.  Level t (m = n-t-2 rows, M = m(m+1)/2, C =
+//     (t+1)M) starts at lr(t) = sum of C below it in the record arrays, at nm4 * lr(t) in d4, at
+//     (t+1) * xpad + 2 lr(t) in d4x and at (t+1) * xpad + sum of m' n (t'+1) below it in pmx
+//     (create_impl's layout, ccj_host.cc Layout): two exclusive scans over the <= 1024 levels in LDS.
+//   * Every workgroup stores 32767 over the interior-loop copies' bound extent (the sentinel pads in
+//     front of every level, the edge pads and every element a reader may meet before this layout's
+//     fill has written it), 16 bytes per lane, when the layout changes.
+// ------------------------------------------------------------------------------------------
+constexpr int BIND_T = 1024;
+struct BindArgs {
+    LevelDesc *lv;
+    long long *lb;
+    LvlDev *ld;
+    LvlX *ldx;
+    int16_t *d4, *x_fill, *pm_fill;
+    long long x_cnt, pm_cnt, xpad;
+    int n, nent, nm4;
+};
+
+__device__ __forceinline__ void bind_fill(int16_t *base, long long cnt, long long tid, long long nth) {
+    const unsigned w = (unsigned)INTERN_INF | ((unsigned)INTERN_INF << 16);
+    const uint4 v = make_uint4(w, w, w, w);
+    uint4 *p = (uint4 *)base;
+    const long long nv = cnt >> 3;
+    for (long long x = tid; x < nv; x += nth) p[x] = v;
+    for (long long x = (nv << 3) + tid; x < cnt; x += nth) base[x] = (int16_t)INTERN_INF;
+}
+
+__global__ __launch_bounds__(BIND_T) void k_bind_layout(BindArgs A) {
+    if (blockIdx.x == 0) {
+        __shared__ long long sc[BIND_T], sp[BIND_T];
+        const int t = threadIdx.x, n = A.n, m = n - t - 2;
+        const bool cells = t < n && m > 0;
+        const long long M = cells ? (long long)m * (m + 1) / 2 : 0, C = (t + 1) * M;
+        const long long P = cells ? (long long)m * n * (t + 1) : 0;
+        sc[t] = C;
+        sp[t] = P;
+        __syncthreads();
+        for (int o = 1; o < BIND_T; o <<= 1) {  // inclusive scans
+            const long long c0 = t >= o ? sc[t - o] : 0, p0 = t >= o ? sp[t - o] : 0;
+            __syncthreads();
+            sc[t] += c0;
+            sp[t] += p0;
+            __syncthreads();
+        }
+        if (t < A.nent) {
+            const long long lr = sc[t] - C, lb = (long long)A.nm4 * lr;
+            A.lv[t] = LevelDesc{A.d4 ? A.d4 + lb : nullptr, (int)C, (int)M, m > 0 ? m : 0, 0};
+            A.lb[t] = lb;
+            A.ld[t] = LvlDev{lb, lr, (int)C, (int)M, {0, 0}};
+            A.ldx[t] = cells ? LvlX{(t + 1) * A.xpad + 2 * lr, (t + 1) * A.xpad + (sp[t] - P)} : LvlX{0, 0};
+        }
+    }
+    const long long nth = (long long)gridDim.x * blockDim.x, tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bind_fill(A.x_fill, A.x_cnt, tid, nth);
+    bind_fill(A.pm_fill, A.pm_cnt, tid, nth);
+}
+
+extern "C" int ccjk_bind_layout(const DevTables *T, int nent, int nm4, LevelDesc *lv, long long *lb, LvlDev *ld, LvlX *ldx,
+                                int16_t *x_fill, long long x_cnt, int16_t *pm_fill, long long pm_cnt, void *stream) {
+    if (nent < 1 || nent > BIND_T || T->n > BIND_T || x_cnt < 0 || pm_cnt < 0 || (((uintptr_t)x_fill | (uintptr_t)pm_fill) & 15))
+        return (int)hipErrorInvalidValue;
+    // 64 bytes per thread and pass; one workgroup when there is nothing to fill
+    const long long vec = (x_cnt + pm_cnt + 7) / 8;
+    const long long blocks = std::max<long long>(1, std::min<long long>(2048, (vec + 4 * BIND_T - 1) / (4 * BIND_T)));
+    const BindArgs A{lv, lb, ld, ldx, T->d4, x_fill, pm_fill, x_cnt, pm_cnt, T->xpad, T->n, nent, nm4};
+    hipLaunchKernelGGL(k_bind_layout, dim3((unsigned)blocks), dim3(BIND_T), 0, (hipStream_t)stream, A);
+    return (int)hipGetLastError();
+}
+
 // narrow levels: split each chunk's a/b loops over up to 8 waves so ~split_target waves run at once
 // (the level schedule, ccj_engine.h)
 extern "C" int ccjk_level_split(int n, int t, int nblk, int split_target) {

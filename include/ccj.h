@@ -108,6 +108,38 @@ int  ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_ctx **out)
  * while a fold is in flight. */
 int  ccj_reset(ccj_ctx *ctx, const char *seq);
 
+/* One context for sequences of any length 1 .. nmax (a mixed-length batch without an allocation per
+ * sequence or a context per length): ccj_create_cap sizes every buffer for the capacity nmax and binds
+ * prob->seq (1 <= length <= nmax, else CCJ_E_ARG); ccj_create(p, o, out) is ccj_create_cap(p, o,
+ * strlen(p->seq), out), and at length == capacity every offset, descriptor and launch is the same.
+ * ccj_rebind binds another sequence of any length up to the capacity; with the bound length it is
+ * ccj_reset.  A rebind allocates nothing and copies nothing synchronously: the level descriptors and
+ * the sentinels of the new layout are written by a kernel on the context's stream (k_bind_layout), the
+ * leader lists and sequence tables go up from pinned staging, and the call waits only where ccj_reset
+ * does (the work-item counts).  CCJ_E_ARG for a longer sequence or a character outside ACGUT,
+ * CCJ_E_STATE while a fold is in flight; a refused rebind leaves the previous binding usable.
+ * ccj_n is the bound length, ccj_capacity the capacity.  ccj_reset still refuses another length.
+ * A band-sharded context (shard_world > 1, simulated or not) holds one length: ccj_create_cap with
+ * nmax != length and a rebind to another length are refused with CCJ_E_ARG. */
+int  ccj_create_cap(const ccj_problem *prob, const ccj_options *opts, int nmax, ccj_ctx **out);
+int  ccj_rebind(ccj_ctx *ctx, const char *seq);
+int  ccj_capacity(const ccj_ctx *ctx);
+/* Element counts of every device buffer whose size depends on n (host helper, no GPU), in the order
+ * of ccj_layout_extent_names() (space separated):
+ *   d4 (int16; 6 per cell, 22 with full4), rec, rk, rl (one 8 / 8 / 4-byte record per cell), acc
+ *   (the partial-record ring, 8-byte slots), d4x, pmx (the interior-loop copies with their pads, int16),
+ *   lord, lord_off (the leader list, int16, and its offsets, int), plane (one 2-D plane, (n+1)(n+2)),
+ *   il, ilseg (candidate-list entries, segment-table words), levels (descriptors), lx (the lx table),
+ *   events (per-level events of each kind), icount (per-level count / offset words),
+ *   ppush_span, iloop_span (bytes a k_ppush / k_iloop wave addresses from one base; must stay < 4 GB).
+ * as_capacity = 0: what a binding of n uses; 1: what a context of capacity n allocates, the maximum
+ * over every length up to n (equal wherever an extent grows with n; the sharing range, and with it
+ * acc, lord and lord_off, moves with n and the target).  split_target: the resolved target (0 = never
+ * split); share: 0 = sharing off; full4: d4 holds all 22 slots.  For an unsharded context.
+ * Returns the entry count and fills out when cap >= it; < 0: bad arguments. */
+int  ccj_layout_extents(int n, int split_target, int share, int full4, int as_capacity, long long *out, int cap);
+const char *ccj_layout_extent_names(void);
+
 /* Run the whole DP fill on the GPU (replaces W_final.cc:60-67).  With host_traceback = 1 it
  * also makes the host mirror valid (ccj_sync_host is implied); by default the matrices stay on
  * the device and the getters copy them on first use. */
