@@ -20,7 +20,7 @@ __all__ = [
     "W_final", "ccj", "load_params", "load_par", "ParFileError", "param_path", "CCJError", "BacktrackExit", "lib", "MAT4", "MAT2",
     "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
-    "SampleExit", "pf_exp_hashes", "load_pfraw",
+    "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -190,6 +190,24 @@ def lib() -> ctypes.CDLL:
     L.ccj_level_schedule.restype = ip
     L.ccj_ctx_level_schedule.argtypes = [vp, ip, ip, ctypes.POINTER(ip)]
     L.ccj_ctx_level_schedule.restype = ip
+    # lockstep batch
+    L.ccj_batch_create.argtypes = [ctypes.POINTER(_Problem), ctypes.POINTER(_Options), ip, ip, ctypes.POINTER(vp)]
+    L.ccj_batch_create.restype = ip
+    L.ccj_batch_bind.argtypes = [vp, ctypes.POINTER(cp), ip]
+    L.ccj_batch_bind.restype = ip
+    for fn in ("ccj_batch_fold_async", "ccj_batch_wait", "ccj_batch_members", "ccj_batch_count"):
+        getattr(L, fn).argtypes = [vp]
+        getattr(L, fn).restype = ip
+    L.ccj_batch_member.argtypes = [vp, ip]
+    L.ccj_batch_member.restype = vp
+    L.ccj_batch_fill_ms.argtypes = [vp]
+    L.ccj_batch_fill_ms.restype = ctypes.c_double
+    L.ccj_batch_last_error.argtypes = [vp]
+    L.ccj_batch_last_error.restype = cp
+    L.ccj_batch_level_plan.argtypes = [ctypes.POINTER(ip), ip, ip, ip, ctypes.POINTER(ip)]
+    L.ccj_batch_level_plan.restype = ip
+    L.ccj_batch_destroy.argtypes = [vp]
+    L.ccj_batch_destroy.restype = None
     L.ccj_params_load_par.argtypes = [cp, cp, cp, cp, ip]
     L.ccj_params_load_par.restype = ip
     L.ccj_params_load_par_string.argtypes = [cp, cp, cp, cp, ip]
@@ -511,7 +529,7 @@ class W_final:
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            lib().ccj_destroy(self._h)
+            lib().ccj_destroy(self._h)  # ignores a lockstep batch's member: LockstepBatch.close frees it
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -519,6 +537,142 @@ class W_final:
             self.close()
         except Exception:
             pass
+
+
+class BatchLevelPlan(tuple):
+    """The batched k_level4d launch of one level (include/ccj.h ccj_batch_level_plan): split (1/2/4/8,
+    0 = no member has the level), threads per block, dynamic LDS bytes, grid x, and per member
+    (workgroups, 64-cell chunks per a-block)."""
+    __slots__ = ()
+    split = property(lambda s: s[0])
+    threads = property(lambda s: s[1])
+    lds = property(lambda s: s[2])
+    grid_x = property(lambda s: s[3])
+    members = property(lambda s: s[4])
+
+
+def batch_level_plan(lengths, t: int, split_target: int = DEFAULT_SPLIT_TARGET) -> BatchLevelPlan:
+    """The one launch a lockstep batch makes for level t of members of these lengths (no GPU needed).
+    split_target is the resolved target: 0 = never split."""
+    lengths = [int(x) for x in lengths]
+    n = (ctypes.c_int * len(lengths))(*lengths)
+    out = (ctypes.c_int * (4 + 2 * len(lengths)))()
+    rc = lib().ccj_batch_level_plan(n, len(lengths), t, split_target, out)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "bad plan arguments")
+    return BatchLevelPlan((out[0], out[1], out[2], out[3],
+                           tuple((out[4 + 2 * k], out[5 + 2 * k]) for k in range(len(lengths)))))
+
+
+class LockstepBatch:
+    """`members` capacity contexts folded in lockstep (include/ccj.h ccj_batch): bind(seqs) gives
+    member k the k-th sequence, fold() runs every bound member's fill, W and traceback in one set of
+    level launches.  Afterwards each bound member (a W_final over the borrowed context) has
+    structure / energy / stdout_msgs set, or `exit` = its BacktrackExit where the reference's
+    backtrack would have exited; result(), hashes(), W(), get2 and get4 work on it."""
+
+    def __init__(self, capacity: int, members: int, dangle: int = 2, params: str | bytes = "DirksPierce09",
+                 noGU: bool = False, device: int = 0, pen=None, **engine):
+        self._blob = params if isinstance(params, (bytes, bytearray)) else load_params(params)
+        self._blob_buf = ctypes.create_string_buffer(bytes(self._blob), len(self._blob))
+        L = lib()
+        self._pen = None
+        if pen is not None:
+            if len(pen) != 14:
+                raise CCJError(CCJ_E_ARG, "pen needs the 14 values of ccj_pk_penalties")
+            self._pen = _Penalties(*[int(v) for v in pen[:12]], float(pen[12]), float(pen[13]))
+        prob = _Problem(None, dangle, 1 if noGU else 0, ctypes.cast(self._blob_buf, ctypes.c_void_p),
+                        ctypes.cast(ctypes.pointer(self._pen), ctypes.c_void_p) if self._pen is not None else None)
+        unknown = set(engine) - {"overlap_d2h", "shard_world", "shard_rank", "shard_simulate", "host_traceback",
+                                 "split_target", "share_splits"}
+        if unknown:
+            raise TypeError(f"LockstepBatch: unknown options {sorted(unknown)}")
+        opts = _Options(device, 1 if engine.get("overlap_d2h") else 0, engine.get("shard_world", 1), engine.get("shard_rank", 0),
+                        1 if engine.get("shard_simulate") else 0, 1 if engine.get("host_traceback") else 0,
+                        engine.get("split_target", 0), engine.get("share_splits", 0))
+        h = ctypes.c_void_p()
+        rc = L.ccj_batch_create(ctypes.byref(prob), ctypes.byref(opts), int(capacity), int(members), ctypes.byref(h))
+        if rc != CCJ_OK:
+            raise CCJError(rc, L.ccj_batch_last_error(None).decode())
+        self._h = h
+        self.capacity = int(capacity)
+        self.dangle = dangle
+        self._all = []
+        for k in range(int(members)):
+            wf = W_final.__new__(W_final)
+            wf._h = ctypes.c_void_p(L.ccj_batch_member(h, k))
+            wf._blob, wf._blob_buf, wf._pen = self._blob, self._blob_buf, self._pen
+            wf.seq, wf.n, wf.dangle = "", 0, dangle
+            wf.structure = wf.energy = wf.exit = None
+            wf.stdout_msgs = ""
+            self._all.append(wf)
+        self.count = 0
+
+    @property
+    def members(self) -> list:
+        """The bound members, in the order of the last bind()."""
+        return self._all[: self.count]
+
+    @property
+    def size(self) -> int:
+        return len(self._all)
+
+    def _check(self, rc: int):
+        if rc != CCJ_OK:
+            raise CCJError(rc, lib().ccj_batch_last_error(self._h).decode())
+
+    def bind(self, seqs) -> None:
+        seqs = [str(s) for s in seqs]
+        arr = (ctypes.c_char_p * max(len(seqs), 1))(*[s.encode() for s in seqs])
+        self._check(lib().ccj_batch_bind(self._h, arr, len(seqs)))
+        self.count = len(seqs)
+        for wf, s in zip(self._all, seqs):
+            wf.seq, wf.n = s, len(s)
+            wf._seq_buf = ctypes.create_string_buffer(s.encode())
+            wf.structure = wf.energy = wf.exit = None
+            wf.stdout_msgs = ""
+
+    def fold_async(self) -> None:
+        self._check(lib().ccj_batch_fold_async(self._h))
+
+    def wait(self) -> None:
+        self._check(lib().ccj_batch_wait(self._h))
+        for wf in self.members:
+            wf.exit = None
+            try:
+                wf.result()
+            except BacktrackExit as ex:
+                wf.structure = wf.energy = None
+                wf.exit = ex
+
+    def fold(self) -> None:
+        self.fold_async()
+        self.wait()
+
+    def fill_ms(self) -> float:
+        return lib().ccj_batch_fill_ms(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            for wf in self._all:
+                wf._h = ctypes.c_void_p()
+            lib().ccj_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plan_lockstep(lengths, k: int) -> list:
+    """The runs fold_many(lockstep=k) folds: the input indices sorted by length (ties in input
+    order) and cut into runs of at most k neighbours, so that the members of one batch have similar
+    lengths.  Pure; every index appears exactly once."""
+    k = max(1, int(k))
+    order = sorted(range(len(lengths)), key=lambda x: (lengths[x], x))
+    return [order[p: p + k] for p in range(0, len(order), k)]
 
 
 def comm_unique_id() -> bytes:
@@ -600,17 +754,41 @@ def layout_extents(n: int, split_target: int = DEFAULT_SPLIT_TARGET, share: bool
     return dict(zip(names, out))
 
 
+def _fold_many_lockstep(seqs, k, dangle, params, noGU, device, capacity, pen, engine) -> list:
+    runs = plan_lockstep([len(s) for s in seqs], k)
+    cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
+    out: list = [None] * len(seqs)
+    batch = LockstepBatch(cap, min(max(1, int(k)), len(seqs)), dangle, params=params, noGU=noGU, device=device, pen=pen, **engine)
+    try:
+        for run in runs:
+            batch.bind([seqs[x] for x in run])
+            batch.fold()
+            for x, wf in zip(run, batch.members):
+                if wf.exit is None:
+                    out[x] = (seqs[x], wf.structure, wf.energy, wf.stdout_msgs, 0, "")
+                else:
+                    out[x] = (seqs[x], None, None, wf.exit.stdout, wf.exit.exit_code, wf.exit.msg)
+    finally:
+        batch.close()
+    return out
+
+
 def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False, device: int = 0,
-              contexts: int = 2, capacity: Optional[int] = None, pen=None, **engine) -> list:
+              contexts: int = 2, capacity: Optional[int] = None, pen=None, lockstep: int = 0, **engine) -> list:
     """Fold sequences of mixed lengths through `contexts` capacity contexts (capacity: the longest
     sequence by default), kept in flight with rebind + fill_async / wait: while one context's
     traceback runs, the next context's fill has the GPU.  Returns one record per sequence, in input
     order: (seq, structure, energy, stdout_msgs, exit_code, stderr).  A reference backtrack exit is
     a record with structure and energy None, its exit code and stderr text; it does not disturb the
-    other folds.  engine: further W_final options (split_target, share_splits, host_traceback, ...)."""
+    other folds.  engine: further W_final options (split_target, share_splits, host_traceback, ...).
+    lockstep=K > 0: instead, sort by length, cut into runs of K neighbours (plan_lockstep) and fold each
+    run as one LockstepBatch, which pays every level's launches once per run; the same records, in
+    input order."""
     seqs = list(seqs)
     if not seqs:
         return []
+    if lockstep and int(lockstep) > 0:
+        return _fold_many_lockstep(seqs, int(lockstep), dangle, params, noGU, device, capacity, pen, engine)
     cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
     k = max(1, min(int(contexts), len(seqs)))
     out: list = [None] * len(seqs)

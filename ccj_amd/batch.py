@@ -1,6 +1,6 @@
 """Fold a file of sequences of mixed lengths through a few capacity contexts (ccj_amd.fold_many).
 
-    python -m ccj_amd.batch [-d N] [-P set] [--noGU] [--contexts K] FILE
+    python -m ccj_amd.batch [-d N] [-P set] [--noGU] [--contexts K] [--lockstep K] FILE
 
 FILE holds one sequence per line, or FASTA records (a '>' header line, then the sequence over one
 or more lines); '-' reads standard input.  Sequences are upper-cased and T becomes U, as the CCJ
@@ -9,7 +9,8 @@ one CCJ run prints for it (cli.fold_cli: side messages, the sequence, "STRUCT (E
 messages where the reference's backtrack exits) and stderr its stderr text; a sequence with a
 character outside GCAU gets the command line's message and counts as exit code 1.  The exit code is
 the largest one seen.  -P names a bundled parameter set or a .ccjp / .par path (default
-DirksPierce09).  Device: $CCJ_DEVICE, else $LOCAL_RANK, else 0.
+DirksPierce09).  --lockstep K folds runs of K sequences of neighbouring length as one lockstep batch
+(fold_many(lockstep=K)); the output is the same bytes.  Device: $CCJ_DEVICE, else $LOCAL_RANK, else 0.
 """
 from __future__ import annotations
 
@@ -58,6 +59,7 @@ def run(argv=None, stdout=None, stderr=None) -> int:
     ap.add_argument("-P", "--paramFile", default="DirksPierce09")
     ap.add_argument("--noGU", action="store_true")
     ap.add_argument("--contexts", type=int, default=2)
+    ap.add_argument("--lockstep", type=int, default=0)
     ap.add_argument("file")
     a = ap.parse_args(argv)
     if a.file == "-":
@@ -73,7 +75,7 @@ def run(argv=None, stdout=None, stderr=None) -> int:
     good = [s for x, s in enumerate(seqs) if x not in bad]
     device = int(os.environ.get("CCJ_DEVICE", os.environ.get("LOCAL_RANK", "0")))
     recs = iter(fold_many(good, a.dangles, params=load_params(a.paramFile), noGU=a.noGU, device=device,
-                          contexts=a.contexts))
+                          contexts=a.contexts, lockstep=a.lockstep))
     code = 0
     for x in range(len(seqs)):
         if x in bad:

@@ -58,6 +58,18 @@ struct BtOut {
     int pad;
 };
 
+// Lockstep batch (ccj_engine.h): where one member's W / traceback launches read and write.  The
+// result arrays are slices of the batch's contiguous buffers, so a fold ends in four copies.
+struct BatchRes {
+    int *W;          // W[0..n]
+    int *S;          // the member's (n+1)*rs ints of W-term scratch
+    int *f_pair;
+    int8_t *f_type;
+    BtOut *out;
+    int cap;         // the member's node-stack capacity
+    int pad;
+};
+
 inline const char *bt_case_name(int type) {
     switch (type) {
         case P_P: return "P_P";
@@ -106,4 +118,7 @@ extern "C" {
 int ccjk_compute_W(const void *T, int *W, int *S, void *stream);  // S: (n+1)*rs ints of scratch
 int ccjk_backtrack(const void *T, const int *W, int *f_pair, int8_t *f_type, ccj::BtOut *out, int stack_cap,
                    void *stream);
+// the same for the `count` members of a lockstep batch, one workgroup each (tabs: DevTables[count])
+int ccjk_compute_W_many(const void *tabs, const ccj::BatchRes *res, int count, int nmax, void *stream);
+int ccjk_backtrack_many(const void *tabs, const ccj::BatchRes *res, int count, int nmax, int nlevmax, int capmax, void *stream);
 }

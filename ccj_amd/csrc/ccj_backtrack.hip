@@ -182,7 +182,7 @@ struct DevExec {
 //   S(k,j) = min(E_ext_Stem(V(k..j) ...), min(P(k,j), P(k+1,j), P(k,j-1), P(k+1,j-1)) + PS),
 // since the reference's two terms share the W[k-1] addend.  k_w_terms evaluates every S(k,j) in
 // parallel; k_compute_W then runs the recurrence in one wave, j ascending, k over the lanes.
-__global__ __launch_bounds__(256) void k_w_terms(DevTables T, int *S) {
+__device__ __forceinline__ void w_terms_body(const DevTables &T, int *S) {
     const int n = T.n;
     DV H{{T, n, T.rs, nullptr, T.S, T.S1, T.pair, T.rtype, T.ld}};
     const int j = blockIdx.y + TURN + 1;
@@ -192,12 +192,18 @@ __global__ __launch_bounds__(256) void k_w_terms(DevTables T, int *S) {
     const int e3 = imin(imin(H.Pg(k, j), H.Pg(k + 1, j)), imin(H.Pg(k, j - 1), H.Pg(k + 1, j - 1))) + T.pen.PS;
     S[(size_t)j * T.rs + k] = imin(e2, e3);
 }
+__global__ __launch_bounds__(256) void k_w_terms(DevTables T, int *S) { w_terms_body(T, S); }
+// Lockstep batch (ccj_engine.h): one launch for every member, the member's tables and result
+// pointers (BatchRes) read at a wave-uniform address; k_w_terms uses y, so the member is z.
+__global__ __launch_bounds__(256) void k_w_terms_many(const DevTables *__restrict__ tabs, const BatchRes *__restrict__ res) {
+    w_terms_body(tabs[blockIdx.z], res[blockIdx.z].S);
+}
 
 // The recurrence with W held in registers: W[x] lives in lane x % 64, slot x / 64 (Q slots cover
 // 0..n), so a step is a register pass plus a wave reduction — no LDS, no barrier — and the S row
 // of step j+1 is loaded while step j reduces, which hides the load latency behind the chain.
 template <int Q>
-__global__ __launch_bounds__(64) void k_compute_W_reg(DevTables T, const int *S, int *Wout) {
+__device__ __forceinline__ void compute_W_reg_body(const DevTables &T, const int *S, int *Wout) {
     const int n = T.n, lane = (int)threadIdx.x;
     int w[Q], s_cur[Q], s_nxt[Q];
     // S(k, j) for k = lane + 64q + 1, which adds to W[k-1] = w[q]; k runs 1 .. j-TURN-1
@@ -231,8 +237,17 @@ __global__ __launch_bounds__(64) void k_compute_W_reg(DevTables T, const int *S,
     for (int q = 0; q < Q; ++q)
         if (lane + 64 * q <= n) Wout[lane + 64 * q] = w[q];
 }
+template <int Q>
+__global__ __launch_bounds__(64) void k_compute_W_reg(DevTables T, const int *S, int *Wout) {
+    compute_W_reg_body<Q>(T, S, Wout);
+}
+// one workgroup per member; Q covers the longest member (slots past a member's n stay unused)
+template <int Q>
+__global__ __launch_bounds__(64) void k_compute_W_reg_many(const DevTables *__restrict__ tabs, const BatchRes *__restrict__ res) {
+    compute_W_reg_body<Q>(tabs[blockIdx.x], res[blockIdx.x].S, res[blockIdx.x].W);
+}
 
-__global__ __launch_bounds__(64) void k_compute_W(DevTables T, const int *S, int *Wout) {
+__device__ __forceinline__ void compute_W_body(const DevTables &T, const int *S, int *Wout) {
     extern __shared__ int Ws[];
     const int n = T.n;
     for (int j = lane_id(); j <= n; j += 64) Ws[j] = 0;
@@ -248,11 +263,15 @@ __global__ __launch_bounds__(64) void k_compute_W(DevTables T, const int *S, int
     }
     for (int j = lane_id(); j <= n; j += 64) Wout[j] = Ws[j];
 }
+__global__ __launch_bounds__(64) void k_compute_W(DevTables T, const int *S, int *Wout) { compute_W_body(T, S, Wout); }
+__global__ __launch_bounds__(64) void k_compute_W_many(const DevTables *__restrict__ tabs, const BatchRes *__restrict__ res) {
+    compute_W_body(tabs[blockIdx.x], res[blockIdx.x].S, res[blockIdx.x].W);
+}
 
 
 // one workgroup of 1..BT_MAXW waves; LDS: the node stack (cap entries)
-__global__ __launch_bounds__(64 * BT_MAXW) void k_backtrack(DevTables T, const int *W, int *f_pair, int8_t *f_type, BtOut *out, int cap,
-                                                            int lds_ld) {
+__device__ __forceinline__ void backtrack_body(const DevTables &T, const int *W, int *f_pair, int8_t *f_type, BtOut *out, int cap,
+                                               int lds_ld) {
     extern __shared__ Interval stk[];
     const int n = T.n;
     // LDS copies of the small tables behind every candidate's first loads (sequence, pair types,
@@ -295,6 +314,16 @@ __global__ __launch_bounds__(64 * BT_MAXW) void k_backtrack(DevTables T, const i
     }
     if (lane_id() == 0) *out = X.st;
 }
+__global__ __launch_bounds__(64 * BT_MAXW) void k_backtrack(DevTables T, const int *W, int *f_pair, int8_t *f_type, BtOut *out, int cap,
+                                                            int lds_ld) {
+    backtrack_body(T, W, f_pair, f_type, out, cap, lds_ld);
+}
+// one workgroup per member: its own stack capacity, inside LDS sized for the largest member
+__global__ __launch_bounds__(64 * BT_MAXW) void k_backtrack_many(const DevTables *__restrict__ tabs, const BatchRes *__restrict__ res,
+                                                                 int lds_ld) {
+    const BatchRes &R = res[blockIdx.x];
+    backtrack_body(tabs[blockIdx.x], R.W, R.f_pair, R.f_type, R.out, R.cap, lds_ld);
+}
 
 }  // namespace
 
@@ -322,14 +351,19 @@ extern "C" int ccjk_compute_W(const void *Tv, int *W, int *S, void *stream) {
     return (int)hipGetLastError();
 }
 
-extern "C" int ccjk_backtrack(const void *Tv, const int *W, int *f_pair, int8_t *f_type, BtOut *out, int stack_cap,
-                              void *stream) {
-    const DevTables *T = (const DevTables *)Tv;
+static int bt_waves() {
     static const int waves = [] {
         const char *e = getenv("CCJ_BT_WAVES");
         const int w = e ? atoi(e) : BT_WAVES_DEFAULT;
         return w < 1 ? 1 : (w > BT_MAXW ? BT_MAXW : w);
     }();
+    return waves;
+}
+
+extern "C" int ccjk_backtrack(const void *Tv, const int *W, int *f_pair, int8_t *f_type, BtOut *out, int stack_cap,
+                              void *stream) {
+    const DevTables *T = (const DevTables *)Tv;
+    const int waves = bt_waves();
     // dynamic LDS: the node stack, then the small tables (k_backtrack); the level descriptors too
     // while the whole stays within 64 KB
     const size_t base = (size_t)stack_cap * sizeof(Interval) + 4 * ((size_t)T->n + 2) + 72 + 16;
@@ -337,5 +371,43 @@ extern "C" int ccjk_backtrack(const void *Tv, const int *W, int *f_pair, int8_t 
     const int lds_ld = with_ld <= 65536 ? 1 : 0;
     hipLaunchKernelGGL(k_backtrack, dim3(1), dim3(64 * waves), lds_ld ? with_ld : base, (hipStream_t)stream, *T, W, f_pair,
                        f_type, out, stack_cap, lds_ld);
+    return (int)hipGetLastError();
+}
+
+// Lockstep batch: W and the traceback of `count` members, one workgroup each (nmax / nlevmax / capmax:
+// the largest member's length, level count and stack capacity; they size the uniform LDS).
+extern "C" int ccjk_compute_W_many(const void *tabs_v, const BatchRes *res, int count, int nmax, void *stream) {
+    const DevTables *tabs = (const DevTables *)tabs_v;
+    const hipStream_t s = (hipStream_t)stream;
+    if (count <= 0) return 0;
+    if (nmax > TURN) {
+        hipLaunchKernelGGL(k_w_terms_many, dim3((unsigned)((nmax + 255) / 256), (unsigned)(nmax - TURN), (unsigned)count), dim3(256), 0,
+                           s, tabs, res);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    const dim3 g((unsigned)count), b(64);
+    switch ((nmax + 64) / 64) {  // slots for W[0..nmax]
+        case 1: hipLaunchKernelGGL(k_compute_W_reg_many<1>, g, b, 0, s, tabs, res); break;
+        case 2: hipLaunchKernelGGL(k_compute_W_reg_many<2>, g, b, 0, s, tabs, res); break;
+        case 3: hipLaunchKernelGGL(k_compute_W_reg_many<3>, g, b, 0, s, tabs, res); break;
+        case 4: hipLaunchKernelGGL(k_compute_W_reg_many<4>, g, b, 0, s, tabs, res); break;
+        case 5: hipLaunchKernelGGL(k_compute_W_reg_many<5>, g, b, 0, s, tabs, res); break;
+        case 6: hipLaunchKernelGGL(k_compute_W_reg_many<6>, g, b, 0, s, tabs, res); break;
+        case 7: hipLaunchKernelGGL(k_compute_W_reg_many<7>, g, b, 0, s, tabs, res); break;
+        case 8: hipLaunchKernelGGL(k_compute_W_reg_many<8>, g, b, 0, s, tabs, res); break;
+        default: hipLaunchKernelGGL(k_compute_W_many, g, b, (nmax + 1) * sizeof(int), s, tabs, res);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_backtrack_many(const void *tabs_v, const BatchRes *res, int count, int nmax, int nlevmax, int capmax,
+                                   void *stream) {
+    if (count <= 0) return 0;
+    const size_t base = (size_t)capmax * sizeof(Interval) + 4 * ((size_t)nmax + 2) + 72 + 16;
+    const size_t with_ld = base + (size_t)nlevmax * sizeof(LvlDev);
+    const int lds_ld = with_ld <= 65536 ? 1 : 0;
+    hipLaunchKernelGGL(k_backtrack_many, dim3((unsigned)count), dim3(64 * bt_waves()), lds_ld ? with_ld : base, (hipStream_t)stream,
+                       (const DevTables *)tabs_v, res, lds_ld);
     return (int)hipGetLastError();
 }

@@ -347,13 +347,17 @@ inline int64_t cell_offset_host(const LevelDesc &L, int x, int a, int h, int i) 
 // ccj_ctx_level_schedule (include/ccj.h) export it.
 
 // narrow levels: split each chunk's a/b loops over up to 8 waves so ~split_target waves run at once
-inline int sched_level_split(int n, int t, int nblk, int split_target) {
-    const int m = n - t - 2;
-    if (m <= 0 || nblk <= 0) return 1;
-    const long waves = (long)nblk * ((m * (m + 1) / 2 + 63) / 64);
+// the split that brings `waves` one-wave chunks to about split_target waves (also what a lockstep
+// batch's level launch takes for the waves of all its members, below)
+inline int sched_split_of(long waves, int split_target) {
     int split = 1;
     while (split_target > 0 && split < 8 && waves * split * 2 <= split_target) split *= 2;
     return split;
+}
+inline int sched_level_split(int n, int t, int nblk, int split_target) {
+    const int m = n - t - 2;
+    if (m <= 0 || nblk <= 0) return 1;
+    return sched_split_of((long)nblk * ((m * (m + 1) / 2 + 63) / 64), split_target);
 }
 
 // The sharing range [g_lo, g_hi): from the first level that runs unsplit (by the whole level's
@@ -419,10 +423,48 @@ inline LevelSched level_sched(int n, int t, int G, int r, int split_target, int 
     return s;
 }
 
+// ---- lockstep batch: K contexts ("members") whose fills advance through the steps
+// s = 0 .. max(n_k)-1 together, every kernel of a step launched once for all of them with the member
+// index as a grid dimension of its own.  The batched entry points (k_*_many) read tabs[member] and
+// the member's own launch arguments of step s from device arrays at wave-uniform addresses and call
+// the same bodies as the single-context entry points, so blockIdx.x stays the member's own block
+// index.  Members never share split points (g_lo = g_hi = 0 in every member's tables, no leader
+// launch): under the default target nothing below n = 159 shares anyway.
+struct LevelArgs {         // one member at step s: level t = s, span sigma = s
+    long long il_first;    // k_iloop: first work item and item count (0: none)
+    int il_nitems;
+    int lv_wavesPerA;      // k_level4d: 64-cell chunks per a-block, a-blocks (0: the member has no level s)
+    int lv_nblk;
+    int pp_ngrp, pp_npairs, pp_blocksA, pp_nout;  // k_ppush(s) (pp_blocksA = 0: none)
+    int dg_nb, dg_blocks;  // k_diag2d(s): interval workgroups, + the table workgroups (0: no span s)
+    int pad;
+};
+static_assert(sizeof(LevelArgs) == 48, "LevelArgs");
+
+// One batched k_level4d launch: block size and dynamic LDS are uniform, so it has ONE split for all
+// members, taken from the launch's total wave count against the same target as sched_level_split
+// (any split is bit-exact: min is order-independent).
+struct BatchLevelPlan {
+    int split, threads, lds, gridx;
+};
+
 }  // namespace ccj
 
 // Kernel launchers (ccj_kernels.hip); all return a hipError_t as int.
 extern "C" {
+// lockstep batch: one member's arguments of step s (everything that follows from n alone, plus its
+// k_iloop items), the level launch's plan (blocks / wpa: per member, may be NULL), and the launches.
+// rows: the step's LevelArgs on the device and the same on the host (for the grid extents).
+void ccjk_batch_args(int n, int s, long long il_first, int il_nitems, ccj::LevelArgs *out);
+ccj::BatchLevelPlan ccjk_batch_level_plan(const int *n, int count, int t, int split_target, int *blocks, int *wpa);
+int ccjk_pre_many(const ccj::DevTables *tabs, int count, int nmax, void *stream);  // k_init2d, k_precompute_ie, k_build_il
+int ccjk_iloop_many(const ccj::DevTables *tabs, const ccj::LevelArgs *row, const ccj::LevelArgs *hrow, int count, int t, void *stream);
+int ccjk_diag2d_many(const ccj::DevTables *tabs, const ccj::LevelArgs *row, const ccj::LevelArgs *hrow, int count, int sigma,
+                     void *stream);
+int ccjk_level4d_many(const ccj::DevTables *tabs, const ccj::LevelArgs *row, const int *n, int count, int t, int split_target,
+                      void *stream);  // n: the members' lengths (host); launches from ccjk_batch_level_plan
+int ccjk_ppush_many(const ccj::DevTables *tabs, const ccj::LevelArgs *row, const ccj::LevelArgs *hrow, int count, int lev,
+                    void *stream);
 int ccjk_init2d(const ccj::DevTables *T, void *stream);
 int ccjk_precompute_ie(const ccj::DevTables *T, void *stream);
 int ccjk_build_il(const ccj::DevTables *T, void *stream);

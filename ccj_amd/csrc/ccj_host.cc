@@ -203,6 +203,12 @@ struct ccj_ctx {
     bool filled = false, mirrored = false, mirrored2d = false;
     bool pending = false;                 // a fill is enqueued and not yet finished (fill_finish)
     bool res_pending = false;             // W + traceback enqueued (result_enqueue), not yet read
+    // a member of a lockstep batch (ccj_batch_create): the batch binds and folds it, its own rebind /
+    // reset / fill calls are refused, and ccj_batch_wait leaves its traceback's outputs in the pinned
+    // result buffers (res_ready), from where ccj_result reports them
+    struct ccj_batch *batch = nullptr;
+    bool member = false;  // set before create_impl: no fill streams or per-level events of its own (the batch has them)
+    bool res_ready = false;
     hipEvent_t ev_res = nullptr;          // device traceback results copied to the pinned buffers
     int *hr_W = nullptr, *hr_fp = nullptr;  // pinned: W, f[].pair, f[].type, the exit record
     int8_t *hr_ft = nullptr;
@@ -975,6 +981,42 @@ static int bind_layout(ccj_ctx *c, int n) {
     return CCJ_OK;
 }
 
+// The fill's own side streams and per-level events of a context (a lockstep batch's members have
+// none: the batch's streams and events run their fills).
+static int create_fill_sync(ccj_ctx *c, size_t nev) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->st_p, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->st_il, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->st_d, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->st_x, hipStreamNonBlocking));
+    // The cross-stream events only order work on this device, so they are recorded without the
+    // default system-scope fence (hipEventDisableSystemFence: fill -0.65 ms at n=200, DESIGN.md §4).
+    // ev_start / ev_end, which the host waits on, keep it.
+    constexpr unsigned fence_fl = (unsigned)hipEventDisableSystemFence;
+    const unsigned sync_fl = hipEventDisableTiming | fence_fl;
+    c->il_done.resize(nev);
+    for (auto &e : c->il_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
+    c->dg_done.resize(nev);
+    for (auto &e : c->dg_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
+    HIPCHK(c, hipEventCreate(&c->ev_start));
+    HIPCHK(c, hipEventCreate(&c->ev_end));
+    HIPCHK(c, hipEventCreate(&c->ev_pre));
+    c->lev_done.resize(nev);
+    // timed: the level durations (mode 1; recording them untimed measured the same)
+    for (auto &e : c->lev_done) HIPCHK(c, hipEventCreateWithFlags(&e, fence_fl));
+    c->p_done.resize(nev);
+    for (auto &e : c->p_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
+    c->pp_done.resize(nev);
+    for (auto &e : c->pp_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
+    c->bulk_done.resize(nev);
+    for (auto &e : c->bulk_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_bpacked, sync_fl));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_bcopied, sync_fl));
+    c->tev.resize(TEV_PER * nev);
+    for (auto &e : c->tev) HIPCHK(c, hipEventCreate(&e));
+    return CCJ_OK;
+}
+
 static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nmax, std::unique_ptr<ccj_ctx> &c, ccj_ctx **out) {
     c->seq = prob->seq;
     const int n = (int)c->seq.size();
@@ -1044,39 +1086,10 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
     ccj_ctx *cp = c.get();
     HIPCHK(cp, hipSetDevice(c->device));
     HIPCHK(cp, hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    HIPCHK(cp, hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking));
-    HIPCHK(cp, hipStreamCreateWithFlags(&c->st_p, hipStreamNonBlocking));
-    HIPCHK(cp, hipStreamCreateWithFlags(&c->st_il, hipStreamNonBlocking));
-    HIPCHK(cp, hipStreamCreateWithFlags(&c->st_d, hipStreamNonBlocking));
-    HIPCHK(cp, hipStreamCreateWithFlags(&c->st_x, hipStreamNonBlocking));
-    // The cross-stream events only order work on this device, so they are recorded without the
-    // default system-scope fence (hipEventDisableSystemFence: fill -0.65 ms at n=200, DESIGN.md §4).
-    // ev_start / ev_end, which the host waits on, keep it.
-    constexpr unsigned fence_fl = (unsigned)hipEventDisableSystemFence;
-    const unsigned sync_fl = hipEventDisableTiming | fence_fl;
-    const size_t nev = (size_t)X[LX_EVENTS];
-    c->il_done.resize(nev);
-    for (auto &e : c->il_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->dg_done.resize(nev);
-    for (auto &e : c->dg_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    HIPCHK(cp, hipEventCreate(&c->ev_start));
-    HIPCHK(cp, hipEventCreate(&c->ev_end));
-    HIPCHK(cp, hipEventCreate(&c->ev_pre));
-    c->lev_done.resize(nev);
-    // timed: the level durations (mode 1; recording them untimed measured the same)
-    for (auto &e : c->lev_done) HIPCHK(cp, hipEventCreateWithFlags(&e, fence_fl));
-    c->p_done.resize(nev);
-    for (auto &e : c->p_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->pp_done.resize(nev);
-    for (auto &e : c->pp_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    c->bulk_done.resize(nev);
-    for (auto &e : c->bulk_done) HIPCHK(cp, hipEventCreateWithFlags(&e, sync_fl));
-    HIPCHK(cp, hipEventCreateWithFlags(&c->ev_bpacked, sync_fl));
-    HIPCHK(cp, hipEventCreateWithFlags(&c->ev_bcopied, sync_fl));
-    c->tev.resize(TEV_PER * nev);
-    for (auto &e : c->tev) HIPCHK(cp, hipEventCreate(&e));
-
     const size_t plane = (size_t)X[LX_PLANE];
+    if (!c->member) {
+        if (const int rc = create_fill_sync(cp, (size_t)X[LX_EVENTS])) return rc;
+    }
     if (X[LX_D4] > 0 && hipMalloc(&c->d4, (size_t)X[LX_D4] * sizeof(int16_t)) != hipSuccess)
         return set_err(cp, CCJ_E_OOM, "device allocation of %.2f GB for 4-D matrices failed", X[LX_D4] * 2e-9);
     // loop records: one RA (8 bytes), RK (8) and RL (4) record per cell, each its own array (ccj_engine.h)
@@ -1263,8 +1276,9 @@ extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_
 }
 
 // ccj_reset (same_length) and ccj_rebind: `what` names the call in the messages
-static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char *what) {
+static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char *what, bool from_batch = false) {
     if (!c || !seq) return CCJ_E_ARG;
+    if (c->batch && !from_batch) return set_err(c, CCJ_E_STATE, "%s: the context is a member of a lockstep batch", what);
     const std::string s(seq);
     const int len = (int)s.size();
     if (same_length && len != c->n)
@@ -1288,6 +1302,7 @@ static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char
     }
     c->seq = s;
     c->W.clear();
+    c->res_ready = false;
     return seq_setup(c);
 }
 
@@ -1669,6 +1684,7 @@ static int fill_finish(ccj_ctx *c) {
 extern "C" int ccj_fill_device(ccj_ctx *c) {
     if (!c) return CCJ_E_ARG;
     if (c->pending || c->res_pending) return set_err(c, CCJ_E_STATE, "ccj_fill_device: a fold is in flight (ccj_wait first)");
+    if (c->batch) return set_err(c, CCJ_E_STATE, "ccj_fill_device: the context is a member of a lockstep batch");
     if (const int rc = fill_enqueue(c)) return rc;
     return fill_finish(c);
 }
@@ -1816,7 +1832,9 @@ extern "C" int ccj_result(ccj_ctx *c, char *structure, double *energy_kcal, char
     if (!c->filled) return set_err(c, CCJ_E_STATE, "ccj_result before ccj_fill");
     std::string st, out;
     int rc = CCJ_OK;
-    if (!c->host_tb) {
+    if (c->res_ready) {  // a batch member: its traceback ran with the batch's (ccj_batch_wait)
+        rc = bt_finish(c, *c->hr_bo, c->hr_fp, st, out);
+    } else if (!c->host_tb) {
         rc = device_result(c, st, out);
     } else {
         if (int e = ensure_mirror(c)) return e;
@@ -1836,6 +1854,7 @@ extern "C" int ccj_result(ccj_ctx *c, char *structure, double *energy_kcal, char
 extern "C" int ccj_fill_async_after(ccj_ctx *c, const ccj_ctx *after) {
     if (!c) return CCJ_E_ARG;
     if (c->pending || c->res_pending) return set_err(c, CCJ_E_STATE, "ccj_fill_async: a fold is already in flight");
+    if (c->batch) return set_err(c, CCJ_E_STATE, "ccj_fill_async: the context is a member of a lockstep batch");
     if (after && after->device != c->device) return set_err(c, CCJ_E_ARG, "ccj_fill_async_after: contexts on different devices");
     if (const int rc = fill_enqueue(c, after)) return rc;
     // the device traceback follows the fill on the same stream; the host traceback needs the mirror
@@ -2265,7 +2284,7 @@ extern "C" int ccj_n(const ccj_ctx *c) { return c ? c->n : 0; }
 extern "C" const char *ccj_last_error(const ccj_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 extern "C" void ccj_destroy(ccj_ctx *c) {
-    if (!c) return;
+    if (!c || c->batch) return;  // a batch member is borrowed: ccj_batch_destroy frees it
     bool leak_send = false;
     if (c->lgroup) {  // leave the in-process group: no member may copy from this context's buffers
         ccj_group *g = c->lgroup;
@@ -2373,4 +2392,349 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
     if (c->st) hipStreamDestroy(c->st);
     if (c->st_copy) hipStreamDestroy(c->st_copy);
     delete c;
+}
+
+// ============================================================================================
+// Lockstep batch (include/ccj.h): K capacity contexts whose fills run as ONE
+// wavefront over the steps s = 0 .. max(n_k)-1.  Every kernel of a step is launched once for all
+// bound members (ccj_engine.h k_*_many), so the per-level chain of launches and events, which is
+// what a short fold costs, is paid once per batch.  The event DAG is fill_enqueue's unsharded one
+// (il_done, lev_done, p_done, dg_done by step) on the batch's own streams.  Members never share
+// split points (created with sharing off: g_lo = g_hi = 0, no leader launch).
+// ============================================================================================
+struct ccj_batch {
+    int device = 0, ncap = 0, K = 0;
+    int count = 0;            // bound members: 0 .. count-1 (the others idle)
+    int nb = 0;               // the longest bound length: steps of a fold
+    int split_target = 0;
+    std::vector<ccj_ctx *> m;
+    std::vector<int> n;       // bound lengths
+    hipStream_t st = nullptr, st_p = nullptr, st_il = nullptr, st_d = nullptr;
+    std::vector<hipEvent_t> il_done, dg_done, lev_done, p_done;
+    hipEvent_t ev_start = nullptr, ev_pre = nullptr, ev_end = nullptr, ev_res = nullptr, ev_args = nullptr;
+    // per member: tables, result pointers; per (step, member): launch arguments; device + pinned staging
+    DevTables *d_tabs = nullptr, *h_tabs = nullptr;
+    BatchRes *d_res = nullptr, *h_res = nullptr;
+    LevelArgs *d_args = nullptr, *h_args = nullptr;
+    // contiguous results, K x (ncap + 1) (BtOut, err: K), so a fold ends in one copy per array
+    int *d_W = nullptr, *d_fp = nullptr, *d_err = nullptr, *h_W = nullptr, *h_fp = nullptr, *h_err = nullptr;
+    int8_t *d_ft = nullptr, *h_ft = nullptr;
+    BtOut *d_bo = nullptr, *h_bo = nullptr;
+    bool pending = false;
+    double fill_ms = 0;
+    std::string err;
+    size_t stride() const { return (size_t)ncap + 1; }
+};
+
+static thread_local std::string g_batch_err;
+
+static int batch_err(ccj_batch *b, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_batch_err = buf;
+    if (b) b->err = buf;
+    return code;
+}
+#define BHIP(b, x)                                                                                  \
+    do {                                                                                            \
+        hipError_t e_ = (x);                                                                        \
+        if (e_ != hipSuccess) return batch_err((b), CCJ_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+
+extern "C" void ccj_batch_destroy(ccj_batch *b) {
+    if (!b) return;
+    hipSetDevice(b->device);
+    for (hipStream_t q : {b->st, b->st_p, b->st_il, b->st_d})
+        if (q) hipStreamSynchronize(q);
+    for (ccj_ctx *c : b->m) {
+        if (!c) continue;
+        // what points into the batch's buffers is the batch's to free
+        c->d_W = c->d_fpair = c->d_err = nullptr;
+        c->d_ftype = nullptr;
+        c->d_btout = nullptr;
+        c->hr_W = c->hr_fp = nullptr;
+        c->hr_ft = nullptr;
+        c->hr_bo = nullptr;
+        c->batch = nullptr;
+        ccj_destroy(c);
+    }
+    hipFree(b->d_tabs);
+    hipFree(b->d_res);
+    hipFree(b->d_args);
+    hipFree(b->d_W);
+    hipFree(b->d_fp);
+    hipFree(b->d_ft);
+    hipFree(b->d_bo);
+    hipFree(b->d_err);
+    for (void *p : {(void *)b->h_tabs, (void *)b->h_res, (void *)b->h_args, (void *)b->h_W, (void *)b->h_fp, (void *)b->h_ft,
+                    (void *)b->h_bo, (void *)b->h_err})
+        if (p) hipHostFree(p);
+    for (auto *v : {&b->il_done, &b->dg_done, &b->lev_done, &b->p_done})
+        for (hipEvent_t e : *v) hipEventDestroy(e);
+    for (hipEvent_t e : {b->ev_start, b->ev_pre, b->ev_end, b->ev_res, b->ev_args})
+        if (e) hipEventDestroy(e);
+    for (hipStream_t q : {b->st, b->st_p, b->st_il, b->st_d})
+        if (q) hipStreamDestroy(q);
+    delete b;
+}
+
+static int batch_create_impl(const ccj_problem *p, const ccj_options *o, int nmax, int members, ccj_batch *b) {
+    b->device = o ? o->device : 0;
+    b->ncap = nmax;
+    b->K = members;
+    BHIP(b, hipSetDevice(b->device));
+    // members: lean d4, device traceback, sharing off, each bound to p->seq (or a placeholder) until
+    // the first ccj_batch_bind
+    ccj_options mo{};
+    if (o) mo = *o;
+    mo.overlap_d2h = 0;
+    mo.share_splits = -1;
+    ccj_problem mp = *p;
+    if (!mp.seq) mp.seq = "A";
+    b->m.assign(members, nullptr);
+    for (int k = 0; k < members; ++k) {
+        std::unique_ptr<ccj_ctx> c(new ccj_ctx());
+        c->member = true;
+        if (const int rc = create_impl(&mp, &mo, nmax, c, &b->m[k])) {
+            const std::string why = c && !c->err.empty() ? c->err : std::string("invalid problem (sequence alphabet, length or parameter blob)");
+            if (c) ccj_destroy(c.release());
+            return batch_err(b, rc, "member %d: %s", k, why.c_str());
+        }
+        if (b->m[k]->full4) return batch_err(b, CCJ_E_ARG, "a lockstep batch needs lean members (CCJ_D4_FULL is set)");
+    }
+    b->split_target = b->m[0]->split_target;
+    for (hipStream_t *q : {&b->st, &b->st_p, &b->st_il, &b->st_d}) BHIP(b, hipStreamCreateWithFlags(q, hipStreamNonBlocking));
+    const unsigned sync_fl = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
+    const size_t nev = (size_t)nmax + 1;
+    for (auto *v : {&b->il_done, &b->dg_done, &b->lev_done, &b->p_done}) {
+        v->assign(nev, nullptr);
+        for (auto &e : *v) BHIP(b, hipEventCreateWithFlags(&e, sync_fl));
+    }
+    BHIP(b, hipEventCreate(&b->ev_start));
+    BHIP(b, hipEventCreate(&b->ev_pre));
+    BHIP(b, hipEventCreate(&b->ev_end));
+    BHIP(b, hipEventCreateWithFlags(&b->ev_res, hipEventDisableTiming));
+    BHIP(b, hipEventCreateWithFlags(&b->ev_args, hipEventDisableTiming));
+    const size_t K = (size_t)members, st = b->stride(), nargs = (size_t)nmax * K;
+    BHIP(b, hipMalloc(&b->d_tabs, K * sizeof(DevTables)));
+    BHIP(b, hipMalloc(&b->d_res, K * sizeof(BatchRes)));
+    BHIP(b, hipMalloc(&b->d_args, nargs * sizeof(LevelArgs)));
+    BHIP(b, hipMalloc(&b->d_W, K * st * sizeof(int)));
+    BHIP(b, hipMalloc(&b->d_fp, K * st * sizeof(int)));
+    BHIP(b, hipMalloc(&b->d_ft, K * st));
+    BHIP(b, hipMalloc(&b->d_bo, K * sizeof(BtOut)));
+    BHIP(b, hipMalloc(&b->d_err, K * sizeof(int)));
+    BHIP(b, hipHostMalloc(&b->h_tabs, K * sizeof(DevTables), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_res, K * sizeof(BatchRes), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_args, nargs * sizeof(LevelArgs), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_W, K * st * sizeof(int), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_fp, K * st * sizeof(int), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_ft, K * st, hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_bo, K * sizeof(BtOut), hipHostMallocDefault));
+    BHIP(b, hipHostMalloc(&b->h_err, K * sizeof(int), hipHostMallocDefault));
+    BHIP(b, hipMemset(b->d_err, 0, K * sizeof(int)));
+    // the members' result arrays and error words become slices of the batch's
+    for (int k = 0; k < members; ++k) {
+        ccj_ctx *c = b->m[k];
+        BHIP(b, hipStreamSynchronize(c->st));  // its creation's setup used d_err
+        hipFree(c->d_W);
+        hipFree(c->d_fpair);
+        hipFree(c->d_ftype);
+        hipFree(c->d_btout);
+        hipFree(c->d_err);
+        c->d_W = b->d_W + k * st;
+        c->d_fpair = b->d_fp + k * st;
+        c->d_ftype = b->d_ft + k * st;
+        c->d_btout = b->d_bo + k;
+        c->d_err = c->T.err = b->d_err + k;
+        c->hr_W = b->h_W + k * st;
+        c->hr_fp = b->h_fp + k * st;
+        c->hr_ft = b->h_ft + k * st;
+        c->hr_bo = b->h_bo + k;
+        c->batch = b;
+    }
+    return CCJ_OK;
+}
+
+extern "C" int ccj_batch_create(const ccj_problem *p, const ccj_options *o, int nmax, int members, ccj_batch **out) {
+    if (!out) return CCJ_E_ARG;
+    *out = nullptr;
+    if (!p || !p->params || nmax < 1 || members < 1) return batch_err(nullptr, CCJ_E_ARG, "ccj_batch_create: bad arguments");
+    if (o && (o->shard_world > 1 || o->host_traceback || o->overlap_d2h || o->share_splits > 0))
+        return batch_err(nullptr, CCJ_E_ARG, "ccj_batch_create: no band sharding, host traceback, host mirror stream or sharing");
+    ccj_batch *b = new ccj_batch();
+    const int rc = batch_create_impl(p, o, nmax, members, b);
+    if (rc != CCJ_OK) {
+        const std::string keep = g_batch_err;
+        ccj_batch_destroy(b);
+        g_batch_err = keep;
+        return rc;
+    }
+    *out = b;
+    return CCJ_OK;
+}
+
+extern "C" const char *ccj_batch_last_error(const ccj_batch *b) { return b ? b->err.c_str() : g_batch_err.c_str(); }
+extern "C" int ccj_batch_members(const ccj_batch *b) { return b ? b->K : 0; }
+extern "C" int ccj_batch_count(const ccj_batch *b) { return b ? b->count : 0; }
+extern "C" ccj_ctx *ccj_batch_member(ccj_batch *b, int k) { return b && k >= 0 && k < b->K ? b->m[k] : nullptr; }
+
+extern "C" int ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count) {
+    if (!b || !seqs) return CCJ_E_ARG;
+    if (b->pending) return batch_err(b, CCJ_E_STATE, "ccj_batch_bind: a fold is in flight (ccj_batch_wait first)");
+    if (count < 1 || count > b->K) return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: count %d outside 1..%d", count, b->K);
+    // every sequence is checked before any member moves: a refused bind leaves the previous binding
+    for (int k = 0; k < count; ++k) {
+        const size_t len = seqs[k] ? strlen(seqs[k]) : 0;
+        if (len < 1 || len > (size_t)b->ncap)
+            return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: sequence %d has length %zu outside 1..%d", k, len, b->ncap);
+        for (const char *q = seqs[k]; *q; ++q)
+            if (!(*q == 'A' || *q == 'C' || *q == 'G' || *q == 'U' || *q == 'T'))
+                return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: invalid character in sequence %d", k);
+    }
+    BHIP(b, hipSetDevice(b->device));
+    const int prev = b->count;
+    b->count = 0;  // unbound until every member is
+    for (int k = 0; k < count; ++k)
+        if (const int rc = rebind_impl(b->m[k], seqs[k], false, "ccj_batch_bind", true))
+            return batch_err(b, rc, "member %d: %s", k, b->m[k]->err.c_str());
+    for (int k = count; k < prev; ++k) b->m[k]->filled = b->m[k]->res_ready = false;  // idle now
+    // tables, result pointers and every step's launch arguments, through pinned staging
+    BHIP(b, hipEventSynchronize(b->ev_args));  // the previous upload has read the staging
+    b->n.assign(count, 0);
+    b->nb = 0;
+    for (int k = 0; k < count; ++k) {
+        ccj_ctx *c = b->m[k];
+        b->n[k] = c->n;
+        b->nb = std::max(b->nb, c->n);
+        b->h_tabs[k] = c->T;
+        b->h_res[k] = BatchRes{c->d_W, c->d_wterm, c->d_fpair, c->d_ftype, c->d_btout, bt_stack_cap(c->n), 0};
+    }
+    const size_t K = (size_t)b->K;
+    for (int s = 0; s < b->nb; ++s)
+        for (int k = 0; k < count; ++k) {
+            const ccj_ctx *c = b->m[k];
+            const bool lev = s < c->nlev && (size_t)s + 1 < c->it_off.size();
+            ccjk_batch_args(c->n, s, lev ? c->it_off[s] : 0, lev ? (int)(c->it_off[s + 1] - c->it_off[s]) : 0, &b->h_args[s * K + k]);
+        }
+    BHIP(b, hipMemcpyAsync(b->d_tabs, b->h_tabs, count * sizeof(DevTables), hipMemcpyHostToDevice, b->st));
+    BHIP(b, hipMemcpyAsync(b->d_res, b->h_res, count * sizeof(BatchRes), hipMemcpyHostToDevice, b->st));
+    BHIP(b, hipMemcpyAsync(b->d_args, b->h_args, (size_t)b->nb * K * sizeof(LevelArgs), hipMemcpyHostToDevice, b->st));
+    BHIP(b, hipEventRecord(b->ev_args, b->st));
+    // the members' own setup (layout kernel, sequence tables, work items) runs on their streams
+    for (int k = 0; k < count; ++k) BHIP(b, hipStreamWaitEvent(b->st, b->m[k]->ev_stage, 0));
+    b->count = count;
+    return CCJ_OK;
+}
+
+extern "C" int ccj_batch_fold_async(ccj_batch *b) {
+    if (!b) return CCJ_E_ARG;
+    if (b->pending) return batch_err(b, CCJ_E_STATE, "ccj_batch_fold_async: a fold is already in flight");
+    if (b->count < 1) return batch_err(b, CCJ_E_STATE, "ccj_batch_fold_async: no binding (ccj_batch_bind first)");
+    BHIP(b, hipSetDevice(b->device));
+    const int cnt = b->count, nb = b->nb, nlev = nb > 2 ? nb - 2 : 0;
+    const size_t K = (size_t)b->K;
+    hipStream_t st = b->st;
+    for (int k = 0; k < cnt; ++k) {
+        ccj_ctx *c = b->m[k];
+        c->filled = c->mirrored = c->mirrored2d = c->res_ready = false;
+    }
+    auto row = [&](int s) { return b->d_args + (size_t)s * K; };
+    auto hrow = [&](int s) { return b->h_args + (size_t)s * K; };
+    BHIP(b, hipMemsetAsync(b->d_err, 0, cnt * sizeof(int), st));
+    BHIP(b, hipEventRecord(b->ev_start, st));
+    BHIP(b, (hipError_t)ccjk_pre_many(b->d_tabs, cnt, nb, st));
+    BHIP(b, hipEventRecord(b->ev_pre, st));
+    BHIP(b, hipStreamWaitEvent(b->st_il, b->ev_pre, 0));
+    BHIP(b, hipStreamWaitEvent(b->st_p, b->ev_pre, 0));
+    // k_diag2d(sg) behind k_iloop(sg+1) on st_il (fill_enqueue's join_diag), after P(sg)
+    auto enqueue_diag = [&](int sg) -> int {
+        if (sg >= 3) BHIP(b, hipStreamWaitEvent(b->st_il, b->p_done[sg], 0));
+        BHIP(b, (hipError_t)ccjk_diag2d_many(b->d_tabs, row(sg), hrow(sg), cnt, sg, b->st_il));
+        BHIP(b, hipEventRecord(b->dg_done[sg], b->st_il));
+        return CCJ_OK;
+    };
+    for (int s = 0; s < nb; ++s) {
+        if (s >= nlev) {
+            if (s == nlev && s >= 1) {
+                if (const int rc = enqueue_diag(s - 1)) return rc;
+            }
+            if (const int rc = enqueue_diag(s)) return rc;
+            continue;
+        }
+        if (s >= 3) BHIP(b, hipStreamWaitEvent(b->st_il, b->lev_done[s - 3], 0));
+        BHIP(b, (hipError_t)ccjk_iloop_many(b->d_tabs, row(s), hrow(s), cnt, s, b->st_il));
+        if (s >= 1) {
+            if (const int rc = enqueue_diag(s - 1)) return rc;
+        }
+        BHIP(b, hipEventRecord(b->il_done[s], b->st_il));
+        BHIP(b, hipStreamWaitEvent(st, b->il_done[s], 0));
+        BHIP(b, (hipError_t)ccjk_level4d_many(b->d_tabs, row(s), b->n.data(), cnt, s, b->split_target, st));
+        BHIP(b, hipEventRecord(b->lev_done[s], st));
+        if (s + 3 < nb) {  // the P terms level s completes: P(s+3)
+            BHIP(b, hipStreamWaitEvent(b->st_p, b->lev_done[s], 0));
+            BHIP(b, (hipError_t)ccjk_ppush_many(b->d_tabs, row(s), hrow(s), cnt, s, b->st_p));
+            BHIP(b, hipEventRecord(b->p_done[s + 3], b->st_p));
+        }
+    }
+    BHIP(b, hipStreamWaitEvent(st, b->dg_done[nb - 1], 0));
+    BHIP(b, hipEventRecord(b->ev_end, st));
+    // W and the traceback, one workgroup per member, then one copy per result array
+    int capmax = 0;
+    for (int k = 0; k < cnt; ++k) capmax = std::max(capmax, bt_stack_cap(b->n[k]));
+    BHIP(b, (hipError_t)ccjk_compute_W_many(b->d_tabs, b->d_res, cnt, nb, st));
+    BHIP(b, (hipError_t)ccjk_backtrack_many(b->d_tabs, b->d_res, cnt, nb, nlev, capmax, st));
+    const size_t ne = (size_t)cnt * b->stride();
+    BHIP(b, hipMemcpyAsync(b->h_W, b->d_W, ne * sizeof(int), hipMemcpyDeviceToHost, st));
+    BHIP(b, hipMemcpyAsync(b->h_fp, b->d_fp, ne * sizeof(int), hipMemcpyDeviceToHost, st));
+    BHIP(b, hipMemcpyAsync(b->h_ft, b->d_ft, ne, hipMemcpyDeviceToHost, st));
+    BHIP(b, hipMemcpyAsync(b->h_bo, b->d_bo, cnt * sizeof(BtOut), hipMemcpyDeviceToHost, st));
+    BHIP(b, hipMemcpyAsync(b->h_err, b->d_err, cnt * sizeof(int), hipMemcpyDeviceToHost, st));
+    BHIP(b, hipEventRecord(b->ev_res, st));
+    b->pending = true;
+    return CCJ_OK;
+}
+
+extern "C" int ccj_batch_wait(ccj_batch *b) {
+    if (!b) return CCJ_E_ARG;
+    if (!b->pending) return batch_err(b, CCJ_E_STATE, "ccj_batch_wait: no fold in flight");
+    b->pending = false;
+    BHIP(b, hipSetDevice(b->device));
+    BHIP(b, hipEventSynchronize(b->ev_res));
+    float ms = 0;
+    BHIP(b, hipEventElapsedTime(&ms, b->ev_start, b->ev_end));
+    b->fill_ms = ms;
+    int rc = CCJ_OK;
+    for (int k = 0; k < b->count; ++k) {
+        ccj_ctx *c = b->m[k];
+        const int herr = b->h_err[k];
+        if (herr) {
+            const int e = (herr & 1) ? set_err(c, CCJ_E_PARAMS, "e_intP table value outside int16 range (flags %d)", herr)
+                                     : set_err(c, CCJ_E_HIP, "device bounds check failed (flags %d)", herr);
+            if (rc == CCJ_OK) rc = batch_err(b, e, "member %d: %s", k, c->err.c_str());
+            continue;
+        }
+        c->fill_ms = ms;
+        c->W.assign(c->hr_W, c->hr_W + c->n + 1);
+        c->bt_steps = c->hr_bo->steps;
+        c->filled = true;
+        c->res_ready = true;
+    }
+    return rc;
+}
+
+extern "C" double ccj_batch_fill_ms(const ccj_batch *b) { return b ? b->fill_ms : 0.0; }
+
+extern "C" int ccj_batch_level_plan(const int *n, int count, int t, int split_target, int *out) {
+    if (!n || !out || count < 1 || t < 0 || split_target < 0) return CCJ_E_ARG;
+    for (int k = 0; k < count; ++k)
+        if (n[k] < 1 || n[k] > 1023) return CCJ_E_ARG;
+    std::vector<int> blocks(count), wpa(count);
+    const BatchLevelPlan P = ccjk_batch_level_plan(n, count, t, split_target, blocks.data(), wpa.data());
+    out[0] = P.split, out[1] = P.threads, out[2] = P.lds, out[3] = P.gridx;
+    for (int k = 0; k < count; ++k) out[4 + 2 * k] = blocks[k], out[5 + 2 * k] = wpa[k];
+    return CCJ_OK;
 }

@@ -11,6 +11,13 @@
 // same-cell reads (PfromL/PfromR/PfromO/PK read PL/PR/PM/PO of the cell) see the finished
 // values and the P?mloop00 seeds see the initial 32767.
 // All arithmetic is int32 min-plus; storage is int16 with the reference clamp at 32767.
+//
+// Every fold kernel's body is a __device__ function over `const DevTables &` with two __global__
+// entry points: the single-context one (DevTables by value in the kernarg) and a batched one
+// (k_*_many) for a lockstep batch (ccj_engine.h), which takes the member from a grid
+// dimension of its own and its tables and per-step arguments from device arrays.  The members of a
+// batch never share split points (g_lo = g_hi = 0, no leader launch): under the default target
+// nothing below n = 159 shares anyway, and sharing on / off is the same fold (tests/test_gpu_share.py).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "ccj_engine.h"
@@ -183,7 +190,7 @@ __device__ int E_MbLoop_d(const DevTables &T, int WM2ij, int WM2ip1j, int WM2ijm
 // ------------------------------------------------------------------------------------------
 // 2-D init: reference initial values (h_struct.hh:100 V = 10000 'N'; matrices.hh:25 INF+1)
 // ------------------------------------------------------------------------------------------
-__global__ void k_init2d(DevTables T, int total) {
+__device__ __forceinline__ void init2d_body(const DevTables &T, int total) {
     for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < total; x += gridDim.x * blockDim.x) {
         T.V[x] = 10000;
         T.Vt[x] = 'N';
@@ -200,6 +207,14 @@ __global__ void k_init2d(DevTables T, int total) {
 #pragma unroll
         for (int f = 0; f < NCF; ++f) T.cf[f * T.tabN + x] = INF;
     }
+}
+__global__ void k_init2d(DevTables T, int total) { init2d_body(T, total); }
+// The lockstep batch's entry points (ccj_engine.h): member = a grid dimension of its own, the
+// member's tables and launch arguments read at a wave-uniform address (scalar loads), then the
+// same body.  A block past its member's extent leaves as a whole workgroup before any barrier.
+__global__ void k_init2d_many(const DevTables *__restrict__ tabs) {
+    const DevTables &T = tabs[blockIdx.y];
+    init2d_body(T, (T.n + 1) * T.rs);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -223,12 +238,14 @@ __device__ __forceinline__ int e_intP(const DevTables &T, int u1, int u2, int p,
     return v;
 }
 
-__global__ void k_precompute_ie(DevTables T) {
+__device__ __forceinline__ void precompute_ie_body(const DevTables &T) {
     const int n = T.n, rs = T.rs;
     const int w = blockIdx.y;  // outer span
     for (int p = 1 + blockIdx.x * blockDim.x + threadIdx.x; p + w <= n; p += gridDim.x * blockDim.x)
         T.ie[(size_t)w * rs + p] = (int16_t)e_intP(T, 0, 0, p, p + w);
 }
+__global__ void k_precompute_ie(DevTables T) { precompute_ie_body(T); }
+__global__ void k_precompute_ie_many(const DevTables *__restrict__ tabs) { precompute_ie_body(tabs[blockIdx.z]); }
 
 // ------------------------------------------------------------------------------------------
 // 2-D anti-diagonal sigma: one 256-thread workgroup per interval (i, l = i+sigma).
@@ -301,7 +318,7 @@ __device__ __forceinline__ void diag2d_cf(const DevTables &T, int sigma, int ite
     for (int f = 0; f < NCF; ++f) T.cf[f * N + cell] = out[f];
 }
 
-__global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, int rank, int nb) {
+__device__ __forceinline__ void diag2d_body(const DevTables &T, int sigma, int G, int rank, int nb) {
 #ifdef CCJ_DEBUG_BOUNDS
     g_dbg_err = T.err;
 #endif
@@ -438,6 +455,15 @@ __global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, i
         }
     }
 }
+__global__ __launch_bounds__(256) void k_diag2d(DevTables T, int sigma, int G, int rank, int nb) {
+    diag2d_body(T, sigma, G, rank, nb);
+}
+__global__ __launch_bounds__(256) void k_diag2d_many(const DevTables *__restrict__ tabs, const LevelArgs *__restrict__ args,
+                                                     int sigma) {
+    const LevelArgs &A = args[blockIdx.y];
+    if ((int)blockIdx.x >= A.dg_blocks) return;  // also a member without span sigma (dg_blocks = 0)
+    diag2d_body(tabs[blockIdx.y], sigma, 1, 0, A.dg_nb);
+}
 
 // readlane of a 64-bit value (two 32-bit readlanes)
 __device__ __forceinline__ unsigned long long rdl64(unsigned long long v, int l) {
@@ -500,8 +526,8 @@ __device__ __forceinline__ int pk_buf(const DevTables &T, __amdgpu_buffer_rsrc_t
 constexpr int PP_OFF = 1 << 30;
 
 template <int PP_S, int PP_U>
-__global__ __launch_bounds__(256) void k_ppush(DevTables T, int lev, int ngrp, int npairs, int hs_len, int blocksA, int G,
-                                               int rank, int nout) {
+__device__ __forceinline__ void ppush_body(const DevTables &T, int lev, int ngrp, int npairs, int hs_len, int blocksA, int G,
+                                           int rank, int nout) {
     TL_STAMP(lev == L_ - 1 ? 5 : lev == L_ ? 6 : -1);
     TL_META(lev);
     const int n = T.n, rs = T.rs;
@@ -652,6 +678,19 @@ __global__ __launch_bounds__(256) void k_ppush(DevTables T, int lev, int ngrp, i
         }
     }
 }
+constexpr int PPUSH_HS = 32;  // inner-loop steps per wave (16 and 64 measured the same)
+template <int PP_S, int PP_U>
+__global__ __launch_bounds__(256) void k_ppush(DevTables T, int lev, int ngrp, int npairs, int hs_len, int blocksA, int G,
+                                               int rank, int nout) {
+    ppush_body<PP_S, PP_U>(T, lev, ngrp, npairs, hs_len, blocksA, G, rank, nout);
+}
+template <int PP_S, int PP_U>
+__global__ __launch_bounds__(256) void k_ppush_many(const DevTables *__restrict__ tabs, const LevelArgs *__restrict__ args,
+                                                    int lev) {
+    const LevelArgs &A = args[blockIdx.y];
+    if ((int)blockIdx.x >= 2 * A.pp_blocksA) return;  // also a member without P terms at lev
+    ppush_body<PP_S, PP_U>(tabs[blockIdx.y], lev, A.pp_ngrp, A.pp_npairs, PPUSH_HS, A.pp_blocksA, 1, 0, A.pp_nout);
+}
 
 // ------------------------------------------------------------------------------------------
 // Interior-loop candidate lists (once per problem, after k_precompute_ie).
@@ -667,11 +706,11 @@ __global__ __launch_bounds__(256) void k_ppush(DevTables T, int lev, int ngrp, i
 // of dt.  One wave per pair: the window's validity and energies are gathered at once (lane = u1)
 // into LDS, then compacted per dt (lane = u1, ballot).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_build_il(DevTables T) {
+__device__ __forceinline__ void build_il_body(const DevTables &T, int kind) {
     __shared__ int16_t es[IE_U][IE_U + 1];  // [u1][u2]: the window's energies
     __shared__ uint32_t vb[IE_U];            // [u1]: bit u2 = the candidate is kept
     const int n = T.n, rs = T.rs;
-    const int p = blockIdx.x + 1, w = blockIdx.y, kind = blockIdx.z;
+    const int p = blockIdx.x + 1, w = blockIdx.y;
     const int q = p + w;
     if (q > n) return;
     // k_iloop reads only the lists of pairs that can pair (its items exist only for those)
@@ -720,6 +759,10 @@ __global__ __launch_bounds__(64) void k_build_il(DevTables T) {
     }
     // null tail: dt 63 addresses the sentinel pad (32767), energy 32767 -> 65534, never below a clamped result
     if (lane < IL_B) ent[cnt + lane] = make_uint2((63u << 21) | (uint32_t)INTERN_INF, 0u);
+}
+__global__ __launch_bounds__(64) void k_build_il(DevTables T) { build_il_body(T, (int)blockIdx.z); }
+__global__ __launch_bounds__(64) void k_build_il_many(const DevTables *__restrict__ tabs) {  // z = 2 * member + kind
+    build_il_body(tabs[blockIdx.z >> 1], (int)(blockIdx.z & 1));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1068,7 +1111,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t il_src(const int16_t *base) {
 // one wave per work item: a closing pair that can pair and up to IL_CW (two 64-lane chunks) of
 // its cells (ccj_items.h, built by k_items in enumeration order)
 constexpr int IL_WPB = 4;  // waves (consecutive items) per k_iloop workgroup (1, 2, 8, 16 measured +3.6 ... +9 ms)
-__global__ __launch_bounds__(64 * IL_WPB) void k_iloop(DevTables T, int t, long long first, int nitems, int G_SH, int rank) {
+__device__ __forceinline__ void iloop_body(const DevTables &T, int t, long long first, int nitems, int G_SH, int rank) {
     TL_STAMP(t >= L_ + 1 && t <= L_ + 3 ? 2 + t - L_ - 1 : -1);
     TL_META(t);
     const int n = T.n, rs = T.rs, m = n - t - 2;
@@ -1204,6 +1247,15 @@ __global__ __launch_bounds__(64 * IL_WPB) void k_iloop(DevTables T, int t, long 
         if (act && gq == 0) dm[a * Lt.M - a] = (int16_t)clamp_store(bm.x);
         if (actb) dm[ab * Lt.M - ab] = (int16_t)clamp_store(bm.y);
     }
+}
+__global__ __launch_bounds__(64 * IL_WPB) void k_iloop(DevTables T, int t, long long first, int nitems, int G_SH, int rank) {
+    iloop_body(T, t, first, nitems, G_SH, rank);
+}
+__global__ __launch_bounds__(64 * IL_WPB) void k_iloop_many(const DevTables *__restrict__ tabs, const LevelArgs *__restrict__ args,
+                                                            int t) {
+    const LevelArgs &A = args[blockIdx.y];
+    if ((int)blockIdx.x * IL_WPB >= A.il_nitems) return;  // also a member without level t (il_nitems = 0)
+    iloop_body(tabs[blockIdx.y], t, A.il_first, A.il_nitems, 1, 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1914,6 +1966,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
 __global__ __launch_bounds__(512) void k_level4d(DevTables T, int t, int wavesPerA, int split, int G, int rank, int nblk, int copies) {
     level4d_body<false>(T, t, wavesPerA, split, G, rank, nblk, copies);
 }
+// the lockstep batch's level launch: one split (block size, LDS) for every member (ccjk_batch_level_plan)
+__global__ __launch_bounds__(512) void k_level4d_many(const DevTables *__restrict__ tabs, const LevelArgs *__restrict__ args, int t,
+                                                      int split) {
+    const LevelArgs &A = args[blockIdx.y];
+    const int cpb = (int)(blockDim.x >> 6) / split;  // chunks per block
+    // whole workgroup, before the split reduction's barrier; also a member without level t (lv_nblk = 0)
+    if ((int)blockIdx.x * cpb >= A.lv_nblk * A.lv_wavesPerA) return;
+    level4d_body<false>(tabs[blockIdx.y], t, A.lv_wavesPerA, split, 1, 0, A.lv_nblk, 1);
+}
 // The leader launch is held at 4 waves per SIMD.  Since the PM / PO multiloop terms left it needs 68
 // VGPRs (122 before) and would fit 7; alternating at n=200 / n=400 (profiles/pmpo_ab.txt): 3 waves
 // 28.0-28.2 / 448-450 ms, 4 waves 27.9-28.1 / 431-432 ms (ahead in every pair), 5 waves 28.8-29.0 /
@@ -2005,24 +2066,32 @@ extern "C" int ccjk_dtail_unpack(const DevTables *T, int sigma, const int16_t *r
     return (int)hipGetLastError();
 }
 
+// k_ppush's launch geometry for rank's share of the terms at lev; false: no term (no launch)
+static bool ppush_geom(int n, int lev, int G, int rank, int &ngrp, int &npairs, int &nout, int &blocksA) {
+    ngrp = npairs = nout = blocksA = 0;
+    const int nmax = imin(lev, n - 4 - lev) + 1;  // t2 values of part A (part B has one fewer or equal)
+    if (nmax <= 0) return false;
+    ngrp = (n - lev - 3 + 63) / 64;
+    // spans per wave = partners per reused level-T load (8; 4 and 16 measured slower) and the
+    // inner-loop slice per wave (32; 16 and 64 measured the same)
+    constexpr int S = PPUSH_S, hs_len = PPUSH_HS;
+    const int nch = (nmax + S - 1) / S;
+    // (chunk, inner-loop slice) pairs, as k_ppush enumerates them
+    for (int c = 0; c < nch; ++c) npairs += (imin((c + 1) * S, nmax) + hs_len - 1) / hs_len;
+    nout = rank <= lev ? (lev - rank) / G + 1 : 0;  // this rank's outer indices r, r+G, ... <= lev
+    if (nout <= 0) return false;
+    blocksA = (npairs * ngrp * nout + 3) / 4;
+    return true;
+}
+
 // P terms of every span whose operands' highest level is lev (k_ppush); completes P(lev+3).
 extern "C" int ccjk_ppush(const DevTables *T, int lev, int G, int rank, void *stream) {
 #ifdef CCJ_ABLATE_PTERM
     return 0;
 #endif
-    const int n = T->n;
-    const int nmax = imin(lev, n - 4 - lev) + 1;  // t2 values of part A (part B has one fewer or equal)
-    if (nmax <= 0) return 0;
-    const int ngrp = (n - lev - 3 + 63) / 64;
-    // spans per wave = partners per reused level-T load (8; 4 and 16 measured slower) and the
-    // inner-loop slice per wave (32; 16 and 64 measured the same)
-    constexpr int S = PPUSH_S, hs_len = 32;
-    const int nch = (nmax + S - 1) / S;
-    int npairs = 0;  // (chunk, inner-loop slice) pairs, as k_ppush enumerates them
-    for (int c = 0; c < nch; ++c) npairs += (imin((c + 1) * S, nmax) + hs_len - 1) / hs_len;
-    const int nout = rank <= lev ? (lev - rank) / G + 1 : 0;  // this rank's outer indices r, r+G, ... <= lev
-    if (nout <= 0) return 0;
-    const int blocksA = (npairs * ngrp * nout + 3) / 4;
+    constexpr int S = PPUSH_S, hs_len = PPUSH_HS;
+    int ngrp, npairs, nout, blocksA;
+    if (!ppush_geom(T->n, lev, G, rank, ngrp, npairs, nout, blocksA)) return 0;
     // split steps in flight per wave: 4 (98 VGPRs) measured 42.1 us per launch standalone vs 53.8 with
     // 2 (62 VGPRs), the same bytes fetched (profiles/r5_ab.txt); CCJ_PP_STEPS=2 for the A/B
     static const int steps = getenv("CCJ_PP_STEPS") ? atoi(getenv("CCJ_PP_STEPS")) : 4;
@@ -2349,6 +2418,111 @@ extern "C" int ccjk_level4d_lead(const DevTables *T, int t, int G, int rank, voi
     const size_t shmem = sp > 1 ? (size_t)(sp - 1) * (LEAD_RED > SPLIT_RED ? LEAD_RED : SPLIT_RED) * 64 * sizeof(int) : 0;
     hipLaunchKernelGGL(k_level4d_lead, dim3((unsigned)waves), dim3(64 * sp), shmem, (hipStream_t)stream, *T, t, wavesPerA,
                        sp, G, rank, nblk, 1);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Lockstep batch (ccj_engine.h): the launches of one step for `count` members.
+// The x extent of a launch is the largest member's (from the host copy of the step's arguments);
+// the member index is y (z where the kernel uses y).
+// ------------------------------------------------------------------------------------------
+extern "C" void ccjk_batch_args(int n, int s, long long il_first, int il_nitems, LevelArgs *out) {
+    LevelArgs A{};
+    const int m = n - s - 2;
+    if (m > 0) {  // level s
+        A.lv_wavesPerA = (m * (m + 1) / 2 + 63) / 64;
+        A.lv_nblk = s + 1;
+        A.il_first = il_first;
+        A.il_nitems = il_nitems > 0 ? il_nitems : 0;
+        int nout;
+        if (!ppush_geom(n, s, 1, 0, A.pp_ngrp, A.pp_npairs, nout, A.pp_blocksA)) A.pp_blocksA = 0;
+        A.pp_nout = nout;
+    }
+    const int nint = n - s;  // span s, as ccjk_diag2d lays its launch out
+    if (nint > 0) {
+        A.dg_nb = nint;
+        A.dg_blocks = nint + (2 * nint + 3) / 4;
+    }
+    *out = A;
+}
+
+// The batched k_level4d launch of level t for members of lengths n[0 .. count): one split from the
+// total wave count; blocks[k] / wpa[k] (may be NULL) = member k's workgroups and chunks per a-block.
+// ccjk_level4d_many launches from it and ccj_batch_level_plan exports it.
+extern "C" BatchLevelPlan ccjk_batch_level_plan(const int *n, int count, int t, int split_target, int *blocks, int *wpa) {
+    long total = 0;
+    for (int k = 0; k < count; ++k) {
+        const int m = n[k] - t - 2;
+        if (m > 0) total += (long)(t + 1) * ((m * (m + 1) / 2 + 63) / 64);
+    }
+    BatchLevelPlan P{0, 0, 0, 0};
+    if (total <= 0 || t < 0) {
+        for (int k = 0; k < count; ++k) {
+            if (blocks) blocks[k] = 0;
+            if (wpa) wpa[k] = 0;
+        }
+        return P;
+    }
+    P.split = sched_split_of(total, split_target);
+    P.threads = P.split <= 4 ? 256 : 64 * P.split;
+    const int cpb = P.threads / 64 / P.split;
+    P.lds = P.split > 1 ? cpb * (P.split - 1) * SPLIT_RED * 64 * (int)sizeof(int) : 0;
+    for (int k = 0; k < count; ++k) {
+        const int m = n[k] - t - 2;
+        const int w = m > 0 ? (m * (m + 1) / 2 + 63) / 64 : 0;
+        const long b = ((long)(m > 0 ? t + 1 : 0) * w + cpb - 1) / cpb;
+        if (blocks) blocks[k] = (int)b;
+        if (wpa) wpa[k] = w;
+        P.gridx = b > P.gridx ? (int)b : P.gridx;
+    }
+    return P;
+}
+
+extern "C" int ccjk_pre_many(const DevTables *tabs, int count, int nmax, void *stream) {
+    if (count <= 0 || nmax < 1) return 0;
+    const hipStream_t s = (hipStream_t)stream;
+    const int total = (nmax + 1) * (nmax + 2);
+    hipLaunchKernelGGL(k_init2d_many, dim3((total + 255) / 256, count), dim3(256), 0, s, tabs);
+    hipLaunchKernelGGL(k_precompute_ie_many, dim3((nmax + 255) / 256, nmax + 1, count), dim3(256), 0, s, tabs);
+    hipLaunchKernelGGL(k_build_il_many, dim3(nmax, nmax + 1, 2 * count), dim3(64), 0, s, tabs);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_iloop_many(const DevTables *tabs, const LevelArgs *row, const LevelArgs *hrow, int count, int t, void *stream) {
+    int gx = 0;
+    for (int k = 0; k < count; ++k) gx = imax(gx, (hrow[k].il_nitems + IL_WPB - 1) / IL_WPB);
+    if (gx <= 0) return 0;
+    hipLaunchKernelGGL(k_iloop_many, dim3(gx, count), dim3(64 * IL_WPB), 0, (hipStream_t)stream, tabs, row, t);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_diag2d_many(const DevTables *tabs, const LevelArgs *row, const LevelArgs *hrow, int count, int sigma,
+                                void *stream) {
+    int gx = 0;
+    for (int k = 0; k < count; ++k) gx = imax(gx, hrow[k].dg_blocks);
+    if (gx <= 0) return 0;
+    hipLaunchKernelGGL(k_diag2d_many, dim3(gx, count), dim3(256), 0, (hipStream_t)stream, tabs, row, sigma);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_level4d_many(const DevTables *tabs, const LevelArgs *row, const int *n, int count, int t, int split_target,
+                                 void *stream) {
+    const BatchLevelPlan P = ccjk_batch_level_plan(n, count, t, split_target, nullptr, nullptr);
+    if (P.gridx <= 0) return 0;
+    hipLaunchKernelGGL(k_level4d_many, dim3((unsigned)P.gridx, count), dim3(P.threads), (size_t)P.lds, (hipStream_t)stream, tabs,
+                       row, t, P.split);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_ppush_many(const DevTables *tabs, const LevelArgs *row, const LevelArgs *hrow, int count, int lev,
+                               void *stream) {
+#ifdef CCJ_ABLATE_PTERM
+    return 0;
+#endif
+    int gx = 0;
+    for (int k = 0; k < count; ++k) gx = imax(gx, 2 * hrow[k].pp_blocksA);
+    if (gx <= 0) return 0;
+    hipLaunchKernelGGL((k_ppush_many<PPUSH_S, 4>), dim3(gx, count), dim3(256), 0, (hipStream_t)stream, tabs, row, lev);
     return (int)hipGetLastError();
 }
 

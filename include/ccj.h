@@ -171,6 +171,45 @@ int  ccj_fill_async(ccj_ctx *ctx);
 int  ccj_fill_async_after(ccj_ctx *ctx, const ccj_ctx *after);
 int  ccj_wait(ccj_ctx *ctx, char *structure, double *energy_kcal, char *stdout_msgs, int msgs_cap);
 
+/* ---- lockstep batch: many short sequences in one set of level launches ----
+ * A short fold costs its chain of per-level launches and events, not its cells.  A lockstep batch is
+ * `members` capacity contexts with one set of parameters, dangles, noGU, penalties and options whose
+ * fills run as ONE wavefront over the levels: every kernel of a level is launched once for all bound
+ * members, with the member index as a grid dimension, so the chain is paid once per batch.  Members
+ * shorter than the longest idle through the late levels (batch sequences of similar length).  The
+ * kernels' arithmetic is the single context's: every result is bit-identical.
+ *   ccj_batch_create: p->seq may be NULL.  CCJ_E_ARG with shard_world > 1, host_traceback,
+ *     overlap_d2h or share_splits > 0 (members never share split points; under the default target
+ *     nothing below n = 159 shares anyway).
+ *   ccj_batch_bind: member k folds seqs[k], 1 <= count <= members, each of length 1 .. nmax; the
+ *     other members idle.  CCJ_E_ARG (sequence too long, character outside ACGUT, bad count) leaves
+ *     the previous binding usable; CCJ_E_STATE while a fold is in flight.
+ *   ccj_batch_fold_async / ccj_batch_wait: enqueue the fill, W and the traceback of every bound
+ *     member / wait for them and check every member's error word.  Afterwards each bound member is in
+ *     the state ccj_wait leaves (filled, result available): ccj_result, the getters, ccj_hashes,
+ *     ccj_sync_host and ccj_n work on it; a member whose traceback ends in a reference exit reports it
+ *     from ccj_result and does not disturb the others.
+ *   ccj_batch_member: borrowed (ccj_destroy ignores it); its own ccj_rebind, ccj_reset and ccj_fill*
+ *     return CCJ_E_STATE while it belongs to the batch.
+ *   ccj_batch_level_plan (host helper, no GPU): the batched k_level4d launch of level t for members of
+ *     lengths n[0 .. count) under the resolved split_target (0 = never split), from the one function
+ *     the launch itself uses: out[0..3] = {split (1, 2, 4, 8; 0: no member has level t), block threads,
+ *     dynamic LDS bytes, grid x}, then per member {workgroups, 64-cell chunks per a-block}; out holds
+ *     4 + 2 * count ints.  One split serves all members: it comes from the launch's total wave count
+ *     against the same target as ccj_level_schedule's. */
+typedef struct ccj_batch ccj_batch;
+int  ccj_batch_create(const ccj_problem *p, const ccj_options *o, int nmax, int members, ccj_batch **out);
+int  ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count);
+int  ccj_batch_fold_async(ccj_batch *b);
+int  ccj_batch_wait(ccj_batch *b);
+ccj_ctx *ccj_batch_member(ccj_batch *b, int k);
+int  ccj_batch_members(const ccj_batch *b);
+int  ccj_batch_count(const ccj_batch *b);              /* bound members */
+double ccj_batch_fill_ms(const ccj_batch *b);          /* the last fold's fill, first launch to last span (ms) */
+const char *ccj_batch_last_error(const ccj_batch *b);  /* b == NULL: the last failed ccj_batch_create */
+int  ccj_batch_level_plan(const int *n, int count, int t, int split_target, int *out);
+void ccj_batch_destroy(ccj_batch *b);
+
 /* Reference getter semantics (matrices.hh:177-182: INF outside i<=j<k-1<=l-1). */
 int  ccj_get4(const ccj_ctx *ctx, int mat, int i, int j, int k, int l);
 /* Raw 2-D value for 1 <= i <= j <= n (ccj_mat2). */
