@@ -21,6 +21,7 @@ __all__ = [
     "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
+    "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -46,6 +47,13 @@ CCJ_E_PF_SAMPLE = 8  # include/ccj_pf.h
 CCJ_OK, CCJ_E_ARG, CCJ_E_OOM, CCJ_E_HIP, CCJ_E_PARAMS, CCJ_E_BACKTRACK, CCJ_E_STATE, CCJ_E_INTER_EXIT = range(8)
 CCJ_E_COMM = 9  # include/ccj.h: band-sharded exchange failed or timed out
 CCJ_E_PARFILE = 8  # include/ccj_parfile.h
+CCJ_E_RANGE = 11  # include/ccj.h: a 4-D value below -32768, no reference-identical result exists
+# include/ccj.h CCJ_RANGE_*: the sites at which a fill saw such a value (W_final.range_flags, RangeError.flags)
+RANGE_LEVEL, RANGE_ILOOP, RANGE_PARTIAL, RANGE_TAB, RANGE_CF = 1, 2, 4, 8, 16
+RANGE_SITES = {"LEVEL": RANGE_LEVEL, "ILOOP": RANGE_ILOOP, "PARTIAL": RANGE_PARTIAL, "TAB": RANGE_TAB, "CF": RANGE_CF}
+# The exit code of a refused fold in fold_many / fold_cli records.  The reference's own paths end
+# with 0 (result, "NOT GOOD RESTR INTER"), 1 (EXIT_FAILURE) or 134 (assert): 3 is none of them.
+RANGE_EXIT_CODE = 3
 
 # name -> blob file (the reference's params/*.par sets, dumped to our table format)
 PARAM_SETS = {
@@ -73,6 +81,16 @@ class BacktrackExit(CCJError):
         super().__init__(code, msg)
         self.exit_code = exit_code
         self.stdout = stdout
+
+
+class RangeError(CCJError):
+    """The fold leaves the domain in which a reference-identical result exists (CCJ_E_RANGE): some
+    4-D value lies below -32768, where the reference's int16 store wraps.  ``flags``: the RANGE_* bits
+    of the sites that saw one.  No structure or energy is reported; the context stays usable."""
+
+    def __init__(self, code: int, msg: str, flags: int):
+        super().__init__(code, msg)
+        self.flags = flags
 
 
 class _Problem(ctypes.Structure):
@@ -160,6 +178,8 @@ def lib() -> ctypes.CDLL:
     L.ccj_last_timing.restype = ip
     L.ccj_last_error.argtypes = [vp]
     L.ccj_last_error.restype = cp
+    L.ccj_range_flags.argtypes = [vp]
+    L.ccj_range_flags.restype = ip
     L.ccj_destroy.argtypes = [vp]
     L.ccj_destroy.restype = None
     L.ccj_num_cells.argtypes = [ip]
@@ -421,8 +441,16 @@ class W_final:
         return lib().ccj_capacity(self._h)
 
     def _check(self, rc: int):
+        if rc == CCJ_E_RANGE:
+            raise RangeError(rc, lib().ccj_last_error(self._h).decode(), self.range_flags())
         if rc != CCJ_OK:
             raise CCJError(rc, lib().ccj_last_error(self._h).decode())
+
+    def range_flags(self) -> int:
+        """The RANGE_* bits of the last fill (include/ccj.h ccj_range_flags): 0 inside the domain of
+        bit-identity.  Non-zero after a RangeError, and after a fold that CCJ_ALLOW_OUT_OF_RANGE=1 let
+        complete under the engine's clamp-only semantics."""
+        return lib().ccj_range_flags(self._h)
 
     def fill(self):
         self._check(lib().ccj_fill(self._h))
@@ -569,7 +597,8 @@ class LockstepBatch:
     member k the k-th sequence, fold() runs every bound member's fill, W and traceback in one set of
     level launches.  Afterwards each bound member (a W_final over the borrowed context) has
     structure / energy / stdout_msgs set, or `exit` = its BacktrackExit where the reference's
-    backtrack would have exited; result(), hashes(), W(), get2 and get4 work on it."""
+    backtrack would have exited, or `refused` = its RangeError where the fold leaves the domain of
+    bit-identity (the other members are untouched); result(), hashes(), W(), get2 and get4 work on it."""
 
     def __init__(self, capacity: int, members: int, dangle: int = 2, params: str | bytes = "DirksPierce09",
                  noGU: bool = False, device: int = 0, pen=None, **engine):
@@ -603,7 +632,7 @@ class LockstepBatch:
             wf._h = ctypes.c_void_p(L.ccj_batch_member(h, k))
             wf._blob, wf._blob_buf, wf._pen = self._blob, self._blob_buf, self._pen
             wf.seq, wf.n, wf.dangle = "", 0, dangle
-            wf.structure = wf.energy = wf.exit = None
+            wf.structure = wf.energy = wf.exit = wf.refused = None
             wf.stdout_msgs = ""
             self._all.append(wf)
         self.count = 0
@@ -629,7 +658,7 @@ class LockstepBatch:
         for wf, s in zip(self._all, seqs):
             wf.seq, wf.n = s, len(s)
             wf._seq_buf = ctypes.create_string_buffer(s.encode())
-            wf.structure = wf.energy = wf.exit = None
+            wf.structure = wf.energy = wf.exit = wf.refused = None
             wf.stdout_msgs = ""
 
     def fold_async(self) -> None:
@@ -638,12 +667,15 @@ class LockstepBatch:
     def wait(self) -> None:
         self._check(lib().ccj_batch_wait(self._h))
         for wf in self.members:
-            wf.exit = None
+            wf.exit = wf.refused = None
             try:
                 wf.result()
             except BacktrackExit as ex:
                 wf.structure = wf.energy = None
                 wf.exit = ex
+            except RangeError as ex:
+                wf.structure = wf.energy = None
+                wf.refused = ex
 
     def fold(self) -> None:
         self.fold_async()
@@ -764,7 +796,9 @@ def _fold_many_lockstep(seqs, k, dangle, params, noGU, device, capacity, pen, en
             batch.bind([seqs[x] for x in run])
             batch.fold()
             for x, wf in zip(run, batch.members):
-                if wf.exit is None:
+                if wf.refused is not None:
+                    out[x] = (seqs[x], None, None, "", RANGE_EXIT_CODE, wf.refused.msg)
+                elif wf.exit is None:
                     out[x] = (seqs[x], wf.structure, wf.energy, wf.stdout_msgs, 0, "")
                 else:
                     out[x] = (seqs[x], None, None, wf.exit.stdout, wf.exit.exit_code, wf.exit.msg)
@@ -780,7 +814,8 @@ def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU
     traceback runs, the next context's fill has the GPU.  Returns one record per sequence, in input
     order: (seq, structure, energy, stdout_msgs, exit_code, stderr).  A reference backtrack exit is
     a record with structure and energy None, its exit code and stderr text; it does not disturb the
-    other folds.  engine: further W_final options (split_target, share_splits, host_traceback, ...).
+    other folds.  Neither does a fold refused with RangeError (possible under non-default pen only):
+    its record is (seq, None, None, "", RANGE_EXIT_CODE, message).  engine: further W_final options (split_target, share_splits, host_traceback, ...).
     lockstep=K > 0: instead, sort by length, cut into runs of K neighbours (plan_lockstep) and fold each
     run as one LockstepBatch, which pays every level's launches once per run; the same records, in
     input order."""
@@ -801,6 +836,8 @@ def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU
             out[x] = (seqs[x], wf.structure, e, wf.stdout_msgs, 0, "")
         except BacktrackExit as ex:
             out[x] = (seqs[x], None, None, ex.stdout, ex.exit_code, ex.msg)
+        except RangeError as ex:
+            out[x] = (seqs[x], None, None, "", RANGE_EXIT_CODE, ex.msg)
 
     try:
         for x, s in enumerate(seqs):

@@ -27,7 +27,7 @@ from __future__ import annotations
 import os
 import sys
 
-from . import BacktrackExit, ParFileError, W_final, load_par
+from . import RANGE_EXIT_CODE, BacktrackExit, ParFileError, RangeError, W_final, load_par
 
 HELP = """Usage: CCJ [options] [sequence]
 Pseudoknotted minimum free energy folding of RNAs
@@ -256,12 +256,16 @@ def _main(a, stdin):
 def fold_cli(seq: str, params, dangles: int, noGU: bool, device: int = 0, pen=None, **engine):
     """One CCJ invocation -> (exit code, stdout text, stderr text), as the reference prints them.
     pen: the 14 pseudoknot penalties (W_final's keyword; None = the reference's defaults); further
-    keywords (host_traceback=...) go to W_final unchanged."""
+    keywords (host_traceback=...) go to W_final unchanged.  A fold refused with RangeError (possible
+    under non-default pen only) gives (RANGE_EXIT_CODE, "", its message): an exit code no reference
+    path uses, and nothing on stdout."""
     wf = W_final(seq, dangles, params=params, noGU=noGU, device=device, pen=pen, **engine)
     try:
         energy = wf.ccj()
     except BacktrackExit as e:
         return e.exit_code, e.stdout, e.msg
+    except RangeError as e:
+        return RANGE_EXIT_CODE, "", e.msg + "\n"
     finally:
         msgs = wf.stdout_msgs
         wf.close()

@@ -68,6 +68,16 @@ static_assert(carrier(PMmloop00) == IN_CF && mslot(PMmloop00) == NMAT4 - NMAT_CF
                   mslot(POmloop10) == NMAT4 - 1,
               "closed-form slots");
 
+// The device error word (DevTables::err).  Bits 1 .. 512 are the parameter and bounds checks; the
+// bits from ERR_RANGE_SHIFT on are the range sites: a 4-D value below -32768 was about
+// to be narrowed to int16, where the reference's store wraps.  (err >> ERR_RANGE_SHIFT) & 31 is what
+// ccj_range_flags reports (include/ccj.h CCJ_RANGE_*).
+constexpr int ERR_RANGE_SHIFT = 10;
+constexpr int ERR_RANGE_LEVEL = 1 << ERR_RANGE_SHIFT, ERR_RANGE_ILOOP = 2 << ERR_RANGE_SHIFT,
+              ERR_RANGE_PARTIAL = 4 << ERR_RANGE_SHIFT, ERR_RANGE_TAB = 8 << ERR_RANGE_SHIFT, ERR_RANGE_CF = 16 << ERR_RANGE_SHIFT;
+constexpr int ERR_RANGE_MASK = 31 << ERR_RANGE_SHIFT;
+constexpr int LOW16 = -32768;  // the lowest value an int16 store keeps
+
 constexpr int IE_U = 29;  // u1,u2 in [0,28] for pseudoknot interior loops (pseudo_loop.cc:694-806)
 #ifndef CCJ_ILB
 #define CCJ_ILB 8
@@ -470,6 +480,14 @@ int ccjk_precompute_ie(const ccj::DevTables *T, void *stream);
 int ccjk_build_il(const ccj::DevTables *T, void *stream);
 int ccjk_iloop(const ccj::DevTables *T, int t, long long first_item, int nitems, int G, int rank, void *stream);
 int ccjk_diag2d(const ccj::DevTables *T, int sigma, int G, int rank, void *stream);
+// the range check of the six closed-form matrices (site CF), after the last k_diag2d on its stream:
+// one workgroup per context / member; nmax = the longest member
+int ccjk_cf_low(const ccj::DevTables *T, void *stream);
+int ccjk_cf_low_many(const ccj::DevTables *tabs, int count, int nmax, void *stream);
+// band-sharded over RCCL: the ranks' LEVEL / ILOOP / PARTIAL bits as one summed 4-byte word (spread:
+// err -> *word, a count field per site; merge: every non-zero field of *word back into err)
+int ccjk_range_spread(const ccj::DevTables *T, unsigned *word, void *stream);
+int ccjk_range_merge(const ccj::DevTables *T, const unsigned *word, void *stream);
 int ccjk_dtail_pack(const ccj::DevTables *T, int sigma, int G, int rank, int16_t *tail, void *stream);
 int ccjk_dtail_unpack(const ccj::DevTables *T, int sigma, const int16_t *recv, size_t slice, size_t off, int G, int rank,
                       void *stream);

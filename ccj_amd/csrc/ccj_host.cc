@@ -63,6 +63,8 @@ struct ccj_group {
     long gen = 0;
     bool broken = false;
     int busy = 0;  // members between taking the peers' send pointers and finishing their copies
+    // the union of the members' range sites (fill_finish): fold k gathers in range_acc[k & 1]
+    int range_acc[2] = {0, 0};
     // false when a member gave up (error or 120 s without the others)
     bool barrier() {
         std::unique_lock<std::mutex> lk(mu);
@@ -202,6 +204,11 @@ struct ccj_ctx {
     std::vector<int> hpt_h;   // pair type table [w][p] host copy (int)
     bool filled = false, mirrored = false, mirrored2d = false;
     bool pending = false;                 // a fill is enqueued and not yet finished (fill_finish)
+    // the last fill's range sites (CCJ_RANGE_*) and whether they refuse its result
+    // (CCJ_E_RANGE; not with CCJ_ALLOW_OUT_OF_RANGE=1)
+    int range_flags = 0;
+    bool range_refused = false;
+    long range_gen = 0;                   // fills finished in an in-process group (ccj_group::range_acc)
     bool res_pending = false;             // W + traceback enqueued (result_enqueue), not yet read
     // a member of a lockstep batch (ccj_batch_create): the batch binds and folds it, its own rebind /
     // reset / fill calls are refused, and ccj_batch_wait leaves its traceback's outputs in the pinned
@@ -749,6 +756,8 @@ static int seq_setup(ccj_ctx *c) {
     HIPCHK(cp, hipEventRecord(c->ev_stage, c->st));
     lap("upload");
     c->filled = c->mirrored = c->mirrored2d = false;
+    c->range_flags = 0;  // a new binding: the last fold's refusal does not stick
+    c->range_refused = false;
     return CCJ_OK;
 }
 
@@ -1115,7 +1124,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
     HIPCHK(cp, hipMalloc(&c->d_pair, 64));
     HIPCHK(cp, hipMalloc(&c->d_rtype, 8));
     HIPCHK(cp, hipMalloc(&c->d_lx, c->lx.size() * sizeof(int)));
-    HIPCHK(cp, hipMalloc(&c->d_err, sizeof(int)));
+    HIPCHK(cp, hipMalloc(&c->d_err, 2 * sizeof(int)));  // the error word; [1]: the sharded range word (fill_enqueue)
     HIPCHK(cp, hipMalloc(&c->d_S, (nmax + 2) * sizeof(short)));
     HIPCHK(cp, hipMalloc(&c->d_S1, (nmax + 2) * sizeof(short)));
     HIPCHK(cp, hipMalloc(&c->d_prm, sizeof(ccj_energy_params)));
@@ -1343,6 +1352,8 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     if (after && after != c && after->ev_end) HIPCHK(c, hipStreamWaitEvent(st, after->ev_end, 0));
     const auto enq0 = std::chrono::steady_clock::now();
     c->filled = c->mirrored = c->mirrored2d = false;
+    c->range_flags = 0;
+    c->range_refused = false;
     HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), st));
     HIPCHK(c, hipEventRecord(c->ev_start, st));
     HIPCHK(c, (hipError_t)ccjk_init2d(&c->T, st));
@@ -1446,6 +1457,11 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
                 HIPCHK(c, (hipError_t)ccjk_diag2d(&c->T, sg, 1, 0, q));
             }
             if (c->level_timing == 2) HIPCHK(c, hipEventRecord(evd[1], q));
+            // behind span n-3, the longest a valid cell's (i,j) or (k,l) can have, on its stream: the
+            // range check of the six closed-form matrices (site CF; every rank holds the
+            // whole tables).  The two spans that follow on this stream are ordered behind it, so the
+            // fill's end (dg_done[n-1]) covers it, and it runs beside the last level.
+            if (sg == n - 3) HIPCHK(c, (hipError_t)ccjk_cf_low(&c->T, q));
             HIPCHK(c, hipEventRecord(c->dg_done[sg], q));
             return CCJ_OK;
         };
@@ -1566,6 +1582,17 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
             HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], c->d4 + c->lv_off[s], bytes, hipMemcpyDeviceToHost, c->st_copy));
         }
     }
+    // band-sharded over RCCL: a rank sees the LEVEL / ILOOP / PARTIAL sites of its own blocks only, so
+    // after the last level the ranks sum one 4-byte word of per-site counts on the level stream's
+    // communicator and every rank ends with the union (the in-process group: fill_finish)
+    if (xchg && !c->lgroup) {
+        if (!c->comm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
+        unsigned *word = (unsigned *)(c->d_err + 1);
+        HIPCHK(c, (hipError_t)ccjk_range_spread(&c->T, word, st));
+        if (ncclAllReduce(word, word, 1, ncclUint32, ncclSum, c->comm, st) != ncclSuccess)
+            return set_err(c, CCJ_E_COMM, "ncclAllReduce (range sites) failed");
+        HIPCHK(c, (hipError_t)ccjk_range_merge(&c->T, word, st));
+    }
     // join: the fill ends when the last level (every rank's part of it) and the last span are done
     HIPCHK(c, hipStreamWaitEvent(st, c->dg_done[n - 1], 0));
     if (xchg && c->nlev >= 1) HIPCHK(c, hipStreamWaitEvent(st, c->bulk_done[c->nlev - 1], 0));
@@ -1612,6 +1639,29 @@ static int wait_fill_end(ccj_ctx *c) {
     }
 }
 
+// CCJ_ALLOW_OUT_OF_RANGE=1 (read at call time): a fold outside the domain completes under the engine's
+// clamp-only semantics instead of being refused
+static bool allow_out_of_range() {
+    const char *e = getenv("CCJ_ALLOW_OUT_OF_RANGE");
+    return e && atoi(e) != 0;
+}
+
+// A finished fill's range sites (CCJ_RANGE_* bits): recorded, and unless allowed they refuse the result.
+static int range_verdict(ccj_ctx *c, int rflags) {
+    c->range_flags = rflags;
+    c->range_refused = rflags != 0 && !allow_out_of_range();
+    if (!c->range_refused) return CCJ_OK;
+    static const char *const site[5] = {"LEVEL", "ILOOP", "PARTIAL", "TAB", "CF"};
+    std::string names;
+    for (int x = 0; x < 5; ++x)
+        if (rflags >> x & 1) names += std::string(names.empty() ? "" : " ") + site[x];
+    return set_err(c, CCJ_E_RANGE,
+                   "a 4-D value lies below -32768 (sites: %s; flags %d): the reference's int16 store wraps there, so no "
+                   "reference-identical result exists for this fold (CCJ_ALLOW_OUT_OF_RANGE=1 folds it clamp-only)",
+                   names.c_str(), rflags);
+}
+static int range_refusal(ccj_ctx *c) { return range_verdict(c, c->range_flags); }
+
 // Wait for an enqueued fill, check the device error word and read its timings.
 static int fill_finish(ccj_ctx *c) {
     if (!c || !c->pending) return c ? set_err(c, CCJ_E_STATE, "no fill in flight") : CCJ_E_ARG;
@@ -1622,7 +1672,27 @@ static int fill_finish(ccj_ctx *c) {
     int herr = 0;
     HIPCHK(c, hipMemcpy(&herr, c->d_err, sizeof(int), hipMemcpyDeviceToHost));
     if (herr & 1) return set_err(c, CCJ_E_PARAMS, "e_intP table value outside int16 range (flags %d)", herr);
-    if (herr) return set_err(c, CCJ_E_HIP, "device bounds check failed (flags %d)", herr);
+    if (herr & ~ERR_RANGE_MASK) return set_err(c, CCJ_E_HIP, "device bounds check failed (flags %d)", herr);
+    int rflags = (herr & ERR_RANGE_MASK) >> ERR_RANGE_SHIFT;
+    if (c->lgroup) {
+        // in-process group: a rank saw the sites of its own blocks; every rank reports the union
+        ccj_group *g = c->lgroup;
+        const int slot = (int)(c->range_gen++ & 1);
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            g->range_acc[slot] |= rflags;
+        }
+        if (!g->barrier()) return set_err(c, CCJ_E_STATE, "local exchange: a group member failed");
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            rflags = g->range_acc[slot];
+        }
+        if (!g->barrier()) return set_err(c, CCJ_E_STATE, "local exchange: a group member failed");
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            g->range_acc[slot] = 0;  // every member, before its next fill's barrier: clean two fills on
+        }
+    }
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_end));
     c->fill_ms = ms;
@@ -1677,8 +1747,8 @@ static int fill_finish(ccj_ctx *c) {
     c->diag_ms = dsum;
     c->il_ms = isum;
     c->pp_ms = psum;
-    c->filled = true;
-    return CCJ_OK;
+    c->filled = true;  // the clamp-only matrices stay readable (getters, ccj_hashes, ccj_sync_host)
+    return range_verdict(c, rflags);
 }
 
 extern "C" int ccj_fill_device(ccj_ctx *c) {
@@ -1830,6 +1900,7 @@ int emit_result(ccj_ctx *c, int rc, const std::string &st, const std::string &ou
 extern "C" int ccj_result(ccj_ctx *c, char *structure, double *energy_kcal, char *msgs, int msgs_cap) {
     if (!c) return CCJ_E_ARG;
     if (!c->filled) return set_err(c, CCJ_E_STATE, "ccj_result before ccj_fill");
+    if (c->range_refused) return range_refusal(c);  // no structure, no energy
     std::string st, out;
     int rc = CCJ_OK;
     if (c->res_ready) {  // a batch member: its traceback ran with the batch's (ccj_batch_wait)
@@ -1867,6 +1938,8 @@ extern "C" int ccj_wait(ccj_ctx *c, char *structure, double *energy_kcal, char *
     if (!c) return CCJ_E_ARG;
     const auto t0 = std::chrono::steady_clock::now();
     if (const int rc = fill_finish(c)) {
+        // a refused fold's traceback is already enqueued (over the clamp-only matrices): let it end
+        if (rc == CCJ_E_RANGE && c->res_pending) hipEventSynchronize(c->ev_res);
         c->res_pending = false;
         return rc;
     }
@@ -2282,6 +2355,7 @@ extern "C" int ccj_comm_init_local(ccj_ctx *c, ccj_group *g) {
 
 extern "C" int ccj_n(const ccj_ctx *c) { return c ? c->n : 0; }
 extern "C" const char *ccj_last_error(const ccj_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
+extern "C" int ccj_range_flags(const ccj_ctx *c) { return c ? c->range_flags : 0; }
 
 extern "C" void ccj_destroy(ccj_ctx *c) {
     if (!c || c->batch) return;  // a batch member is borrowed: ccj_batch_destroy frees it
@@ -2680,6 +2754,9 @@ extern "C" int ccj_batch_fold_async(ccj_batch *b) {
             BHIP(b, hipEventRecord(b->p_done[s + 3], b->st_p));
         }
     }
+    // behind the last span on its stream: every member's closed-form range check (site CF)
+    BHIP(b, (hipError_t)ccjk_cf_low_many(b->d_tabs, cnt, nb, b->st_il));
+    BHIP(b, hipEventRecord(b->dg_done[nb - 1], b->st_il));
     BHIP(b, hipStreamWaitEvent(st, b->dg_done[nb - 1], 0));
     BHIP(b, hipEventRecord(b->ev_end, st));
     // W and the traceback, one workgroup per member, then one copy per result array
@@ -2711,7 +2788,9 @@ extern "C" int ccj_batch_wait(ccj_batch *b) {
     for (int k = 0; k < b->count; ++k) {
         ccj_ctx *c = b->m[k];
         const int herr = b->h_err[k];
-        if (herr) {
+        c->range_flags = 0;
+        c->range_refused = false;
+        if (herr & ~ERR_RANGE_MASK) {
             const int e = (herr & 1) ? set_err(c, CCJ_E_PARAMS, "e_intP table value outside int16 range (flags %d)", herr)
                                      : set_err(c, CCJ_E_HIP, "device bounds check failed (flags %d)", herr);
             if (rc == CCJ_OK) rc = batch_err(b, e, "member %d: %s", k, c->err.c_str());
@@ -2722,6 +2801,9 @@ extern "C" int ccj_batch_wait(ccj_batch *b) {
         c->bt_steps = c->hr_bo->steps;
         c->filled = true;
         c->res_ready = true;
+        // a member outside the domain is its own affair, like a reference backtrack exit: the batch is
+        // fine, its ccj_result returns CCJ_E_RANGE
+        range_verdict(c, (herr & ERR_RANGE_MASK) >> ERR_RANGE_SHIFT);
     }
     return rc;
 }

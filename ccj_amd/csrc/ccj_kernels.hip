@@ -282,6 +282,12 @@ __device__ __forceinline__ void diag2d_tables(const DevTables &T, int sigma, int
     }
     const int cell = w * rs + p;
     const int v[6] = {L.m00, L.m01, L.m10, R.m00, R.m01, R.m10};
+    // range site TAB: an entry stands for the store of every valid cell that has its
+    // interval, so it counts only if there is one: (i,j) = (p,q) needs q <= n-2, (k,l) = (p,q) needs
+    // p >= 3.  (The other entries, the longest intervals, feed no entry that counts.)
+    const int lowL = q <= n - 2 ? imin(L.m00, imin(L.m01, L.m10)) : 0;
+    const int lowR = p >= 3 ? imin(R.m00, imin(R.m01, R.m10)) : 0;
+    if (imin(lowL, lowR) < LOW16) atomicOr(T.err, ERR_RANGE_TAB);
 #pragma unroll
     for (int f = 0; f < 6; ++f) T.tab[f * T.tabN + cell] = (int16_t)mloop2d_store(v[f]);
 }
@@ -463,6 +469,107 @@ __global__ __launch_bounds__(256) void k_diag2d_many(const DevTables *__restrict
     const LevelArgs &A = args[blockIdx.y];
     if ((int)blockIdx.x >= A.dg_blocks) return;  // also a member without span sigma (dg_blocks = 0)
     diag2d_body(tabs[blockIdx.y], sigma, 1, 0, A.dg_nb);
+}
+
+// ------------------------------------------------------------------------------------------
+// Range site CF: no kernel evaluates the six PM / PO closed forms per cell, so whether
+// one of them falls below -32768 at a valid cell is decided from the nine tables, by the reduction of
+// ccj_pmpo2d.h (pmpo2d_branch): one workgroup, after the last k_diag2d of the fill on its stream.
+//   1. fm[f][j] = min_{i<=j} f(i,j) for j <= n-2 and gm[g][k] = min_{l>=k} g(k,l) for k >= 3, every
+//      table entry of the spans <= n-3 read once (lanes along p: coalesced), LDS minima
+//   2. fm[f][.] becomes its prefix minimum over j (one thread per array)
+//   3. per k and branch: const + fm[f][k-2] + gm[g][k], minimum per matrix
+// The term kinds a branch uses on its (i,j) side / its (k,l) side, in LDS slot order:
+constexpr int CFL_T = 1024;
+constexpr int CFL_NF = 6, CFL_NG = 8;
+__host__ __device__ constexpr int cfl_fkind(int s) {
+    return s == 0 ? CF_A : s == 1 ? CF_AO : s == 2 ? CF_UP : s == 3 ? CF_UO : s == 4 ? CF_ZERO : CF_CPSPAN;
+}
+__host__ __device__ constexpr int cfl_gkind(int s) {
+    return s == 0 ? CF_AO : s == 1 ? CF_CPSPAN : s == 2 ? CF_Y : s == 3 ? CF_CL : s == 4 ? CF_Z : s == 5 ? CF_A : s == 6 ? CF_XO : CF_ZO;
+}
+__device__ __forceinline__ int cfl_fslot(int kind) {
+    int r = -1;
+#pragma unroll
+    for (int s = 0; s < CFL_NF; ++s) r = cfl_fkind(s) == kind ? s : r;
+    return r;
+}
+__device__ __forceinline__ int cfl_gslot(int kind) {
+    int r = -1;
+#pragma unroll
+    for (int s = 0; s < CFL_NG; ++s) r = cfl_gkind(s) == kind ? s : r;
+    return r;
+}
+__host__ __device__ constexpr size_t cfl_lds_ints(int n) { return (size_t)(CFL_NF + CFL_NG) * (n + 2) + 6; }
+
+__device__ __forceinline__ void cf_low_body(const DevTables &T) {
+    extern __shared__ int cfl[];  // fm[CFL_NF][n+2], gm[CFL_NG][n+2], res[6]
+    const int n = T.n, rs = T.rs, st = n + 2, tid = threadIdx.x, nt = blockDim.x;
+    if (n < 3) return;  // no valid cell (whole workgroup)
+    int *fm = cfl, *gm = cfl + CFL_NF * st, *res = gm + CFL_NG * st;
+    const int cp = T.pen.cp;
+    const long long N = T.tabN;
+    const int *__restrict__ cf = T.cf;
+    for (int x = tid; x < (int)cfl_lds_ints(n); x += nt) cfl[x] = INF;
+    __syncthreads();
+    for (int e = tid; e < (n - 2) * rs; e += nt) {  // e = w * rs + p, spans w <= n-3
+        const int w = e / rs, p = e - w * rs, q = p + w;
+        if (p < 1 || q > n) continue;
+        int ent[NCF];
+#pragma unroll
+        for (int f = 0; f < NCF; ++f) ent[f] = cf[f * N + e];
+        if (q <= n - 2) {  // (i,j) = (p,q) has a valid cell
+#pragma unroll
+            for (int s = 0; s < CFL_NF; ++s)
+                atomicMin(&fm[s * st + q], pmpo2d_term(cfl_fkind(s), cp, w, cfl_fkind(s) < NCF ? ent[cfl_fkind(s)] : 0));
+        }
+        if (p >= 3) {  // (k,l) = (p,q) has a valid cell
+#pragma unroll
+            for (int s = 0; s < CFL_NG; ++s)
+                atomicMin(&gm[s * st + p], pmpo2d_term(cfl_gkind(s), cp, w, cfl_gkind(s) < NCF ? ent[cfl_gkind(s)] : 0));
+        }
+    }
+    __syncthreads();
+    if ((tid & 63) == 0 && (tid >> 6) < CFL_NF) {  // one wave per array
+        int *a = fm + (tid >> 6) * st;
+        int run = INF;
+        for (int j = 1; j <= n - 2; ++j) {
+            run = imin(run, a[j]);
+            a[j] = run;
+        }
+    }
+    __syncthreads();
+    for (int k = 3 + tid; k <= n; k += nt) {
+#pragma unroll
+        for (int br = 0; br < CF_NBR; ++br) {
+            int mat6, f, g;
+            bool seeded;
+            pmpo2d_branch(br, mat6, seeded, f, g);
+            const int v = pmpo2d_branch_const(seeded, T.pen.bp) + fm[cfl_fslot(f) * st + k - 2] + gm[cfl_gslot(g) * st + k];
+            if (v < LOW16) atomicMin(&res[mat6], v);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int low = 0;
+#pragma unroll
+        for (int x = 0; x < 6; ++x) low = imin(low, res[x]);
+        if (low < LOW16) atomicOr(T.err, ERR_RANGE_CF);
+    }
+}
+__global__ __launch_bounds__(CFL_T) void k_cf_low(DevTables T) { cf_low_body(T); }
+__global__ __launch_bounds__(CFL_T) void k_cf_low_many(const DevTables *__restrict__ tabs) { cf_low_body(tabs[blockIdx.x]); }
+
+// band-sharded over RCCL: the sites a rank sees only for its own blocks, as a count field each, so
+// that one summed 4-byte word carries their union (world <= 255)
+__global__ void k_range_spread(DevTables T, unsigned *word) {
+    const int e = *T.err;
+    *word = (e & ERR_RANGE_LEVEL ? 1u : 0u) | (e & ERR_RANGE_ILOOP ? 1u << 8 : 0u) | (e & ERR_RANGE_PARTIAL ? 1u << 16 : 0u);
+}
+__global__ void k_range_merge(DevTables T, const unsigned *word) {
+    const unsigned w = *word;
+    const int e = (w & 0xffu ? ERR_RANGE_LEVEL : 0) | (w & 0xff00u ? ERR_RANGE_ILOOP : 0) | (w & 0xff0000u ? ERR_RANGE_PARTIAL : 0);
+    if (e) atomicOr(T.err, e);
 }
 
 // readlane of a 64-bit value (two 32-bit readlanes)
@@ -1162,6 +1269,8 @@ __device__ __forceinline__ void iloop_body(const DevTables &T, int t, long long 
             return;
         }
 #endif
+        // range site ILOOP: the level kernel reads these minima back as int16
+        if ((act && gq == 0 && bm.x < LOW16) || (actb && bm.y < LOW16)) atomicOr(T.err, ERR_RANGE_ILOOP);
         int16_t *dl = T.d4 + Lt.lb + (long long)mslot(PL) * Lt.C + a * Lt.M + i - 1;
         if (act && gq == 0) dl[h * m - ((h * (h - 1)) >> 1)] = (int16_t)clamp_store(bm.x);
         if (actb) dl[hb * m - ((hb * (hb - 1)) >> 1)] = (int16_t)clamp_store(bm.y);
@@ -1199,6 +1308,7 @@ __device__ __forceinline__ void iloop_body(const DevTables &T, int t, long long 
             return;
         }
 #endif
+        if ((act && gq == 0 && bm.x < LOW16) || (actb && bm.y < LOW16)) atomicOr(T.err, ERR_RANGE_ILOOP);
         int16_t *dr = T.d4 + Lt.lb + (long long)mslot(PR) * Lt.C + a * Lt.M;
         if (act && gq == 0) dr[h * m - ((h * (h - 1)) >> 1) + i - 1] = (int16_t)clamp_store(bm.x);
         if (actb) dr[hb * m - ((hb * (hb - 1)) >> 1) + ib - 1] = (int16_t)clamp_store(bm.y);
@@ -1243,6 +1353,7 @@ __device__ __forceinline__ void iloop_body(const DevTables &T, int t, long long 
             return;
         }
 #endif
+        if ((act && gq == 0 && bm.x < LOW16) || (actb && bm.y < LOW16)) atomicOr(T.err, ERR_RANGE_ILOOP);
         int16_t *dm = T.d4 + Lt.lb + (long long)mslot(PM) * Lt.C + h * m - ((h * (h - 1)) >> 1) + j - 1;
         if (act && gq == 0) dm[a * Lt.M - a] = (int16_t)clamp_store(bm.x);
         if (actb) dm[ab * Lt.M - ab] = (int16_t)clamp_store(bm.y);
@@ -1270,11 +1381,18 @@ constexpr int LEAD_RED = (LA_I + LA_J > LB_K + LB_L ? LA_I + LA_J : LB_K + LB_L)
 // ints per lane a split wave of the plain loops hands to part 0 (the accumulators of both loops)
 constexpr int SPLIT_RED = 10;
 
-// partial record: up to 3 int16 fields (min-clamped like a store), the others 32767
-__device__ __forceinline__ uint2 pack_acc(const int *f, int nf) {
-    int c[4];
+// partial record: up to 3 int16 fields (min-clamped like a store), the others 32767.
+// Range site PARTIAL: every call packs for a follower cell that exists and takes the
+// record (level4d_body writes no other), and that cell's own value is <= its partial, so a field
+// below -32768 is a low store of that cell, which its int16 field would hide from the LEVEL check.
+__device__ __forceinline__ uint2 pack_acc(const DevTables &T, const int *f, int nf) {
+    int c[4], low = 0;
 #pragma unroll
-    for (int x = 0; x < 4; ++x) c[x] = x < nf ? clamp_store(f[x]) : INTERN_INF;
+    for (int x = 0; x < 4; ++x) {
+        c[x] = x < nf ? clamp_store(f[x]) : INTERN_INF;
+        low = imin(low, c[x]);
+    }
+    if (low < LOW16) atomicOr(T.err, ERR_RANGE_PARTIAL);
     return make_uint2(pk16(c[0], c[1]), pk16(c[2], c[3]));
 }
 
@@ -1586,13 +1704,13 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             if (i - r >= 1) {
                 const unsigned idx = (unsigned)((a + r) * Mf) + L0 - (unsigned)(r * (h + 1));
                 CHKA(idx);
-                ((unsigned *)(ring + (long long)AI * T.accC))[idx] = pack_acc(AI_[r], LA_I).x;  // 4-byte records, dense
+                ((unsigned *)(ring + (long long)AI * T.accC))[idx] = pack_acc(T, AI_[r], LA_I).x;  // 4-byte records, dense
             }
             if (h - r >= 0) {
                 const int hh = h - r;
                 const unsigned idx = (unsigned)((a + r) * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                ring[(long long)AJ * T.accC + idx] = pack_acc(AJ_[r], LA_J);
+                ring[(long long)AJ * T.accC + idx] = pack_acc(T, AJ_[r], LA_J);
             }
         }
     };
@@ -1760,12 +1878,12 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                 const int hh = h - r;
                 const unsigned idx = (unsigned)(a * Mf + hh * mf - ((hh * (hh - 1)) >> 1) + i - 1);
                 CHKA(idx);
-                ring[(long long)AK * T.accC + idx] = pack_acc(AK_[r], LB_K);
+                ring[(long long)AK * T.accC + idx] = pack_acc(T, AK_[r], LB_K);
             }
             if (i <= m - h - r) {  // l side
                 const unsigned idx = (unsigned)(a * Mf) + L0 - (unsigned)(h * r);
                 CHKA(idx);
-                ((unsigned *)(ring + (long long)AL * T.accC))[idx] = pack_acc(AL_[r], LB_L).x;  // 4-byte records, dense
+                ((unsigned *)(ring + (long long)AL * T.accC))[idx] = pack_acc(T, AL_[r], LB_L).x;  // 4-byte records, dense
             }
         }
     };
@@ -1942,6 +2060,11 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     dst[mslot(PfromM) * C] = (int16_t)clamp_store(vPfromM);
     if (T.full4) dst[mslot(PfromMprime) * C] = (int16_t)clamp_store(vPfromMp);
     if (T.full4) dst[mslot(PfromO) * C] = (int16_t)clamp_store(vPfromO);
+    // range site LEVEL: the ten values this cell stores, before the clamp (behind the
+    // stores: nothing waits for the compare)
+    if (imin(imin(imin(vPK, vPL), imin(vPR, vPM)), imin(imin(imin(vPO, vPfromL), imin(vPfromR, vPfromM)), imin(vPfromMp, vPfromO))) <
+        LOW16)
+        atomicOr(T.err, ERR_RANGE_LEVEL);
     // loop records and interior-loop copies (the copies only where a later k_iloop can read them:
     // its pair can pair); in sharded fills the other ranks' cells get both from k_unpack
     if (!copies) return;
@@ -2013,6 +2136,25 @@ extern "C" int ccjk_diag2d(const DevTables *T, int sigma, int G, int rank, void 
     const int ntab = nint > 0 ? (2 * nint + 3) / 4 : 0;
     if (nb + ntab <= 0) return 0;
     hipLaunchKernelGGL(k_diag2d, dim3(nb + ntab), dim3(256), 0, (hipStream_t)stream, *T, sigma, G, rank, nb);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_cf_low(const DevTables *T, void *stream) {
+    if (T->n < 3) return 0;
+    hipLaunchKernelGGL(k_cf_low, dim3(1), dim3(CFL_T), cfl_lds_ints(T->n) * sizeof(int), (hipStream_t)stream, *T);
+    return (int)hipGetLastError();
+}
+extern "C" int ccjk_cf_low_many(const DevTables *tabs, int count, int nmax, void *stream) {
+    if (count < 1 || nmax < 3) return 0;
+    hipLaunchKernelGGL(k_cf_low_many, dim3(count), dim3(CFL_T), cfl_lds_ints(nmax) * sizeof(int), (hipStream_t)stream, tabs);
+    return (int)hipGetLastError();
+}
+extern "C" int ccjk_range_spread(const DevTables *T, unsigned *word, void *stream) {
+    hipLaunchKernelGGL(k_range_spread, dim3(1), dim3(1), 0, (hipStream_t)stream, *T, word);
+    return (int)hipGetLastError();
+}
+extern "C" int ccjk_range_merge(const DevTables *T, const unsigned *word, void *stream) {
+    hipLaunchKernelGGL(k_range_merge, dim3(1), dim3(1), 0, (hipStream_t)stream, *T, word);
     return (int)hipGetLastError();
 }
 

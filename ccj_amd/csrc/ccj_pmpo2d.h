@@ -112,6 +112,81 @@ CCJ_HD int pmpo2d_eval(int x, int bp, int cp, const TAB &tab, int i, int j, int 
     }
 }
 
+// ---- the lowest pre-clamp value of the six matrices over the valid cells (site CF) ----
+// Wherever the inner expression F of cl(F) above is below 32767 it is the value Matrix4D::set is
+// handed, so "some valid cell of matrix x is stored from a value below -32768" is min F < -32768 over
+// the valid cells 1 <= i <= j, j+2 <= k <= l <= n.  F is the minimum of one or two branches
+// const + f(i,j) + g(k,l); a branch's minimum under k >= j+2 is
+//   const + min_{k=3..n} ( min_{j<=k-2} min_{i<=j} f(i,j)  +  min_{l>=k} g(k,l) ).
+// An interval that belongs to no valid cell ((i,j) with j > n-2, (k,l) with k < 3) never enters.
+// The branches are listed once here; the host reduction below and k_cf_low walk the same list.
+constexpr int CF_NBR = 9;                              // branches of the six formulas
+constexpr int CF_ZERO = NCF, CF_CPSPAN = NCF + 1;      // term kinds beside the tables: 0, min(0, cp * span)
+constexpr int CF_NKIND = NCF + 2;
+// branch br: the matrix it belongs to (0..5 = PMmloop00/01/10, POmloop00/01/10), whether its constant
+// is the seed s (else the restart 32767), and the kinds of its (i,j) and (k,l) terms
+CCJ_HD void pmpo2d_branch(int br, int &mat6, bool &seeded, int &f, int &g) {
+    switch (br) {
+        case 0: mat6 = 0; seeded = true; f = CF_A; g = CF_AO; break;
+        case 1: mat6 = 1; seeded = false; f = CF_ZERO; g = CF_CPSPAN; break;
+        case 2: mat6 = 1; seeded = true; f = CF_A; g = CF_Y; break;
+        case 3: mat6 = 2; seeded = false; f = CF_CPSPAN; g = CF_CL; break;
+        case 4: mat6 = 2; seeded = true; f = CF_UP; g = CF_Z; break;
+        case 5: mat6 = 3; seeded = true; f = CF_AO; g = CF_A; break;
+        case 6: mat6 = 4; seeded = true; f = CF_AO; g = CF_XO; break;
+        case 7: mat6 = 5; seeded = false; f = CF_ZERO; g = CF_CL; break;
+        default: mat6 = 5; seeded = true; f = CF_UO; g = CF_ZO; break;
+    }
+}
+CCJ_HD int pmpo2d_branch_const(bool seeded, int bp) { return seeded ? pmpo2d_seed(bp) : INTERN_INF; }
+// a term of kind `kind` at interval (p,q) from its table entry (unused for the two table-free kinds)
+CCJ_HD int pmpo2d_term(int kind, int cp, int span, int entry) {
+    return kind == CF_ZERO ? 0 : kind == CF_CPSPAN ? imin(0, cp * span) : entry;
+}
+
+// F of matrix mat6 at one cell from the branch list: pmpo2d_eval's value before its outer cl()
+template <class TAB>
+CCJ_HD int pmpo2d_inner(int mat6, int bp, int cp, const TAB &tab, int i, int j, int k, int l) {
+    int v = 3 * INF;
+    for (int br = 0; br < CF_NBR; ++br) {
+        int m, f, g;
+        bool seeded;
+        pmpo2d_branch(br, m, seeded, f, g);
+        if (m != mat6) continue;
+        v = imin(v, pmpo2d_branch_const(seeded, bp) + pmpo2d_term(f, cp, j - i, f < NCF ? tab(f, i, j) : 0) +
+                        pmpo2d_term(g, cp, l - k, g < NCF ? tab(g, k, l) : 0));
+    }
+    return v;
+}
+
+// Host: out6[x] = the minimum of F over the valid cells (INF when there is none, n < 3), by the
+// reduction above: O(n^2) table reads per branch.  tab(f, p, q) as for pmpo2d_eval.
+template <class TAB>
+inline void pmpo2d_low_host(int n, int bp, int cp, const TAB &tab, int out6[6]) {
+    for (int x = 0; x < 6; ++x) out6[x] = INF;
+    if (n < 3) return;
+    int *pre = new int[n + 1];
+    for (int br = 0; br < CF_NBR; ++br) {
+        int mat6, f, g;
+        bool seeded;
+        pmpo2d_branch(br, mat6, seeded, f, g);
+        pre[0] = INF;
+        for (int j = 1; j <= n - 2; ++j) {
+            int fm = INF;
+            for (int i = 1; i <= j; ++i) fm = imin(fm, pmpo2d_term(f, cp, j - i, f < NCF ? tab(f, i, j) : 0));
+            pre[j] = imin(pre[j - 1], fm);
+        }
+        int best = 3 * INF;
+        for (int k = 3; k <= n; ++k) {
+            int gm = INF;
+            for (int l = k; l <= n; ++l) gm = imin(gm, pmpo2d_term(g, cp, l - k, g < NCF ? tab(g, k, l) : 0));
+            best = imin(best, pre[k - 2] + gm);
+        }
+        out6[mat6] = imin(out6[mat6], pmpo2d_branch_const(seeded, bp) + best);
+    }
+    delete[] pre;
+}
+
 // Host: all nine tables of a sequence from its raw WBP, wbp[(q-p)*rs + p] for 1 <= p <= q <= n (rs >= n+2),
 // into tabs[f*N + (q-p)*rs + p].  The device fill computes the same entries span by span (k_diag2d).
 inline void pmpo2d_host_tables(int n, int rs, int cp, const int *wbp, int *tabs, long long N) {

@@ -38,6 +38,32 @@ extern "C" {
                                 progress within CCJ_COMM_TIMEOUT_S seconds (default 300; a peer rank
                                 died or hung); the communicator is aborted and the context must be
                                 destroyed */
+#define CCJ_E_RANGE     11   /* the fold leaves the domain in which a reference-identical result exists:
+                                some 4-D value lies below -32768 before it is stored, where the
+                                reference's int16 assignment (matrices.hh:188-191) wraps.  The fill
+                                detects it exactly and ccj_fill / ccj_fill_device /
+                                ccj_wait / ccj_result return this code and report no structure or
+                                energy; ccj_range_flags names the detection sites.  The context stays
+                                usable (ccj_reset, ccj_rebind), and the getters, ccj_hashes and
+                                ccj_sync_host still serve the clamp-only matrices the fill computed.
+                                With CCJ_ALLOW_OUT_OF_RANGE=1 in the environment (read at call time)
+                                the fold completes under those clamp-only semantics instead, and
+                                ccj_range_flags still reports. */
+
+/* Where the last fill of the context saw a 4-D value below -32768 (0: the fold lies inside the
+ * domain and the result is the reference's, bit for bit).  One bit per kind of place where the
+ * engine narrows to int16 or stands in for a per-cell store:
+ *   LEVEL   the ten values a level-kernel cell stores
+ *   ILOOP   an interior-loop minimum of PL / PR / PM handed to the level kernel as int16
+ *   PARTIAL a leader's partial minimum packed as int16 for a follower cell
+ *   TAB     an entry of the six PL / PR multiloop tables that belongs to a valid cell
+ *   CF      a PM / PO multiloop closed form at a valid cell
+ * A band-sharded rank reports the union over all ranks. */
+#define CCJ_RANGE_LEVEL   1
+#define CCJ_RANGE_ILOOP   2
+#define CCJ_RANGE_PARTIAL 4
+#define CCJ_RANGE_TAB     8
+#define CCJ_RANGE_CF      16
 
 /* 4-D gap matrices, reference pseudo_loop.hh:62-108 / allocation order pseudo_loop.cc:37-62 */
 enum ccj_mat4 {
@@ -188,7 +214,8 @@ int  ccj_wait(ccj_ctx *ctx, char *structure, double *energy_kcal, char *stdout_m
  *     member / wait for them and check every member's error word.  Afterwards each bound member is in
  *     the state ccj_wait leaves (filled, result available): ccj_result, the getters, ccj_hashes,
  *     ccj_sync_host and ccj_n work on it; a member whose traceback ends in a reference exit reports it
- *     from ccj_result and does not disturb the others.
+ *     from ccj_result and does not disturb the others.  Likewise a member whose fold leaves the domain
+ *     (CCJ_E_RANGE above): ccj_batch_wait returns CCJ_OK, that member's ccj_result CCJ_E_RANGE.
  *   ccj_batch_member: borrowed (ccj_destroy ignores it); its own ccj_rebind, ccj_reset and ccj_fill*
  *     return CCJ_E_STATE while it belongs to the batch.
  *   ccj_batch_level_plan (host helper, no GPU): the batched k_level4d launch of level t for members of
@@ -306,6 +333,9 @@ int  ccj_work_model_seq(const char *seq, int noGU, double *out4);
 
 int  ccj_n(const ccj_ctx *ctx);
 const char *ccj_last_error(const ccj_ctx *ctx);
+/* The CCJ_RANGE_* bits of the context's last fill (above); 0 inside the domain, before any fill and
+ * for a NULL context.  A lockstep batch's member reports its own fold's. */
+int  ccj_range_flags(const ccj_ctx *ctx);
 void ccj_destroy(ccj_ctx *ctx);
 
 /* Number of 4-D DP cells (unit of work): C(n+1,4). */
@@ -317,6 +347,14 @@ uint64_t ccj_num_cells(int n);
  * valid cell in the order i, j >= i, k >= j+2, l >= k (l fastest).  Returns the cells per matrix
  * (out may be NULL to count), or -1. */
 long long ccj_pmpo2d_closed(int n, const int *wbp, int bp, int cp, int16_t *out, long long cells);
+/* From the same inputs, out6[x] = the lowest value of matrix x (the same order) over the valid cells
+ * before the store's clamp at 32767 (INF when n has no valid cell): the fold's CCJ_RANGE_CF bit is
+ * "some out6[x] < -32768".  O(n^2) per formula branch, not O(n^4).  Returns 0, or -1. */
+int  ccj_pmpo2d_low(int n, const int *wbp, int bp, int cp, int *out6);
+/* The same minima cell by cell, O(n^4) (tests): over the valid cells, or with valid_only = 0 over every
+ * pair of intervals (i,j), (k,l) whether or not they form a cell.  -2: the formulas' branch list
+ * disagrees with ccj_pmpo2d_closed's evaluator at some valid cell. */
+int  ccj_pmpo2d_low_brute(int n, const int *wbp, int bp, int cp, int valid_only, int *out6);
 
 #ifdef __cplusplus
 }
