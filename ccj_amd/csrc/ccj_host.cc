@@ -89,6 +89,35 @@ struct ccj_group {
 // edge exchange's start (band-sharded), [7,8] k_ppush, [9,10] the bulk exchange (band-sharded, st_x)
 constexpr int TEV_PER = 11;
 
+// What a fill's graph orders itself with: the side streams, the per-level events and
+// the fill's start / setup / end.  A context that is no batch member owns one, a lockstep batch owns
+// one for all its members.  The level stream stays with its owner (a context also sets up on it).
+struct FillSync {
+    hipStream_t st_p = nullptr, st_il = nullptr;
+    std::vector<hipEvent_t> il_done, dg_done;  // k_iloop(t) / k_diag2d(sigma) finished
+    std::vector<hipEvent_t> lev_done;
+    std::vector<hipEvent_t> p_done;            // P(sigma) reduced
+    hipEvent_t ev_start = nullptr, ev_pre = nullptr, ev_end = nullptr;
+};
+
+// Band-sharded exchange: what only a context with world > 1 that does not simulate
+// has (ccj_ctx::exchanges); nothing in it exists for any other context.
+struct Exchange {
+    hipStream_t st_d = nullptr;          // k_diag2d, each span partitioned by rank
+    hipStream_t st_x = nullptr;          // the bulk part of each level's exchange
+    std::vector<hipEvent_t> bulk_done;   // level t complete on this rank (bulk part unpacked)
+    std::vector<hipEvent_t> pp_done;     // this rank's P-term push of span sigma done (before the exchange)
+    // in-process group: this rank's bulk slice packed / the peers' bulk slices copied (reused every level;
+    // the group's barriers order each record before the peers' waits on it)
+    hipEvent_t ev_bpacked = nullptr, ev_bcopied = nullptr;
+    // per part (XCH_EDGE, XCH_BULK): own slice, world slices
+    int16_t *d_send[2] = {nullptr, nullptr}, *d_recv[2] = {nullptr, nullptr};
+    std::vector<int> xnmax[2];           // per level: the largest rank's block count of the part (slice = 22 x nmax x M + tail)
+    ccj_group *lgroup = nullptr;         // in-process exchange between contexts (tests), else RCCL
+    ncclComm_t comm = nullptr;           // the edge all-gathers (level stream)
+    ncclComm_t comm_b = nullptr;         // the bulk all-gathers (st_x), split from comm: one communicator per stream
+};
+
 struct ccj_ctx {
     // problem
     int n = 0;
@@ -114,8 +143,7 @@ struct ccj_ctx {
     // kernel family launch (k_diag2d, k_iloop, the level span).  The markers of mode 2 are barrier
     // packets on the streams and cost ~3 ms per n=200 fill, so the default is 1.
     int level_timing = 1;
-    ncclComm_t comm = nullptr;    // the edge all-gathers (level stream)
-    ncclComm_t comm_b = nullptr;  // the bulk all-gathers (st_x), split from comm: one communicator per stream
+    bool exchanges() const { return world > 1 && !simulate; }  // band-sharded with an exchange
 
     // layout
     std::vector<LevelDesc> lv_host;     // device pointers
@@ -162,10 +190,6 @@ struct ccj_ctx {
     int16_t *d_dummy = nullptr;
     uint32_t *d_items = nullptr;          // k_iloop work items, all levels back to back
     size_t items_cap = 0;
-    // band-sharded exchange, per part (XCH_EDGE, XCH_BULK): own slice, world slices
-    int16_t *d_send[2] = {nullptr, nullptr}, *d_recv[2] = {nullptr, nullptr};
-    std::vector<int> xnmax[2];            // per level: the largest rank's block count of the part (slice = 22 x nmax x M + tail)
-    ccj_group *lgroup = nullptr;          // in-process exchange between contexts (tests), else RCCL
     long long *d_icount = nullptr, *d_ioff = nullptr;  // k_items: items per (t, r), first item
     long long *h_ioff = nullptr;          // pinned staging of it_off
     long long *h_icount = nullptr;        // pinned landing of the k_items counts (so the copy is asynchronous)
@@ -181,20 +205,11 @@ struct ccj_ctx {
     BtOut *d_btout = nullptr;
     std::vector<unsigned long long> h_pk;
     int8_t *d_vt = nullptr;
-    hipStream_t st = nullptr, st_copy = nullptr, st_p = nullptr, st_il = nullptr, st_d = nullptr;
-    hipStream_t st_x = nullptr;          // band-sharded: the bulk part of each level's exchange
-    std::vector<hipEvent_t> bulk_done;   // band-sharded: level t complete on this rank (bulk part unpacked)
-    // in-process group: this rank's bulk slice packed / the peers' bulk slices copied (reused every level;
-    // the group's barriers order each record before the peers' waits on it)
-    hipEvent_t ev_bpacked = nullptr, ev_bcopied = nullptr;
-    bool join_diag = true;               // k_diag2d(t-1) after k_iloop(t) on st_il (one cross-stream wait per level)
-    std::vector<hipEvent_t> p_done;  // P(sigma) reduced
-    std::vector<hipEvent_t> pp_done; // band-sharded: this rank's P-term push of span sigma done (before the exchange)
+    hipStream_t st = nullptr, st_copy = nullptr;
+    FillSync fs;   // none for a lockstep batch's member: the batch's runs its fill
+    Exchange xch;  // exchanges() only
     std::vector<double> lev_ms_v, diag_ms_v, il_ms_v, xch_ms_v, xbulk_ms_v, pp_ms_v;
-    std::vector<hipEvent_t> il_done, dg_done;  // k_iloop(t) / k_diag2d(sigma) finished
-    std::vector<hipEvent_t> lev_done;
     std::vector<hipEvent_t> tev;  // timing events (TEV_PER per level): 2 per k_level4d, k_iloop, k_diag2d and k_ppush launch
-    hipEvent_t ev_start = nullptr, ev_end = nullptr, ev_pre = nullptr;
     DevTables T{};
 
     // host mirror
@@ -251,7 +266,39 @@ int set_err(ccj_ctx *c, int code, const char *fmt, ...) {
         hipError_t e_ = (x);                                                                             \
         if (e_ != hipSuccess) return set_err((ctx), CCJ_E_HIP, "%s: %s", #x, hipGetErrorString(e_));     \
     } while (0)
+// inside a function that returns the hipError_t itself (the caller reports it: HIPCHK, BHIP)
+#define HIPTRY(x)                                  \
+    do {                                           \
+        const hipError_t e_ = (hipError_t)(x);     \
+        if (e_ != hipSuccess) return e_;           \
+    } while (0)
 
+// The cross-stream events only order work on one device, so they are recorded without the default
+// system-scope fence (hipEventDisableSystemFence: fill -0.65 ms at n=200).  ev_start /
+// ev_pre / ev_end, which the host waits on or times, keep it.  timed_levels: lev_done can be timed
+// (a context's level durations, timing mode 1; recording them untimed measured the same).
+constexpr unsigned EV_ORDER_TIMED = (unsigned)hipEventDisableSystemFence, EV_ORDER = hipEventDisableTiming | EV_ORDER_TIMED;
+hipError_t fill_sync_create(FillSync &f, size_t nev, bool timed_levels) {
+    HIPTRY(hipStreamCreateWithFlags(&f.st_p, hipStreamNonBlocking));
+    HIPTRY(hipStreamCreateWithFlags(&f.st_il, hipStreamNonBlocking));
+    for (auto *v : {&f.il_done, &f.dg_done, &f.lev_done, &f.p_done}) {
+        v->assign(nev, nullptr);
+        for (auto &e : *v) HIPTRY(hipEventCreateWithFlags(&e, timed_levels && v == &f.lev_done ? EV_ORDER_TIMED : EV_ORDER));
+    }
+    for (hipEvent_t *e : {&f.ev_start, &f.ev_pre, &f.ev_end}) HIPTRY(hipEventCreate(e));
+    return hipSuccess;
+}
+
+// after the owner has synchronised the streams
+void fill_sync_destroy(FillSync &f) {
+    for (auto *v : {&f.il_done, &f.dg_done, &f.lev_done, &f.p_done})
+        for (hipEvent_t e : *v)
+            if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {f.ev_start, f.ev_pre, f.ev_end})
+        if (e) hipEventDestroy(e);
+    for (hipStream_t q : {f.st_p, f.st_il})
+        if (q) hipStreamDestroy(q);
+}
 
 // --------------------------------------------------------------------------------------------
 // host energy helpers
@@ -499,7 +546,7 @@ static thread_local std::string g_create_err;
 // packed slice of the part into its own receive buffer (same device) on stream q, between two
 // barriers, so no slice is overwritten by the part's next pack before every member has read it.
 static int local_allgather(ccj_ctx *c, int part, size_t slice, hipStream_t q) {
-    ccj_group *g = c->lgroup;
+    ccj_group *g = c->xch.lgroup;
     HIPCHK(c, hipStreamSynchronize(q));  // own slice packed
     if (!g->barrier()) return set_err(c, CCJ_E_STATE, "local exchange: a group member failed");
     // take the peers' send buffers under the lock and hold the group busy until the copies are
@@ -513,13 +560,13 @@ static int local_allgather(ccj_ctx *c, int part, size_t slice, hipStream_t q) {
                 g->cv.notify_all();
                 return set_err(c, CCJ_E_STATE, "local exchange: rank %d has no context", r);
             }
-            src[r] = g->members[r]->d_send[part];
+            src[r] = g->members[r]->xch.d_send[part];
         }
         ++g->busy;
     }
     hipError_t e = hipSuccess;
     for (int r = 0; r < g->world && e == hipSuccess; ++r)
-        e = hipMemcpyAsync(c->d_recv[part] + (size_t)r * slice, src[r], slice * sizeof(int16_t), hipMemcpyDeviceToDevice, q);
+        e = hipMemcpyAsync(c->xch.d_recv[part] + (size_t)r * slice, src[r], slice * sizeof(int16_t), hipMemcpyDeviceToDevice, q);
     const hipError_t e2 = hipStreamSynchronize(q);
     {
         std::lock_guard<std::mutex> lk(g->mu);
@@ -538,7 +585,7 @@ static int local_allgather(ccj_ctx *c, int part, size_t slice, hipStream_t q) {
 // (a member's next bulk pack waits for every member's ev_bcopied, bulk_start).  The level chain keeps
 // running meanwhile; only the edge part (local_allgather) synchronises the host with the level.
 static int local_bulk_gather(ccj_ctx *c, size_t slice) {
-    ccj_group *g = c->lgroup;
+    ccj_group *g = c->xch.lgroup;
     if (!g->barrier()) return set_err(c, CCJ_E_STATE, "local exchange: a group member failed");
     std::lock_guard<std::mutex> lk(g->mu);
     for (int r = 0; r < g->world; ++r) {
@@ -548,19 +595,19 @@ static int local_bulk_gather(ccj_ctx *c, size_t slice) {
             g->cv.notify_all();
             return set_err(c, CCJ_E_STATE, "local exchange: rank %d has no context", r);
         }
-        HIPCHK(c, hipStreamWaitEvent(c->st_x, p->ev_bpacked, 0));
-        HIPCHK(c, hipMemcpyAsync(c->d_recv[XCH_BULK] + (size_t)r * slice, p->d_send[XCH_BULK], slice * sizeof(int16_t),
-                                 hipMemcpyDeviceToDevice, c->st_x));
+        HIPCHK(c, hipStreamWaitEvent(c->xch.st_x, p->xch.ev_bpacked, 0));
+        HIPCHK(c, hipMemcpyAsync(c->xch.d_recv[XCH_BULK] + (size_t)r * slice, p->xch.d_send[XCH_BULK], slice * sizeof(int16_t),
+                                 hipMemcpyDeviceToDevice, c->xch.st_x));
     }
-    HIPCHK(c, hipEventRecord(c->ev_bcopied, c->st_x));
+    HIPCHK(c, hipEventRecord(c->xch.ev_bcopied, c->xch.st_x));
     return CCJ_OK;
 }
 // before this member's next bulk pack overwrites its send slice: every member's copies of it are done
 static int local_bulk_wait_copied(ccj_ctx *c) {
-    ccj_group *g = c->lgroup;
+    ccj_group *g = c->xch.lgroup;
     std::lock_guard<std::mutex> lk(g->mu);
     for (int r = 0; r < g->world; ++r)
-        if (const ccj_ctx *p = g->members[r]) HIPCHK(c, hipStreamWaitEvent(c->st_x, p->ev_bcopied, 0));
+        if (const ccj_ctx *p = g->members[r]) HIPCHK(c, hipStreamWaitEvent(c->xch.st_x, p->xch.ev_bcopied, 0));
     return CCJ_OK;
 }
 
@@ -994,33 +1041,18 @@ static int bind_layout(ccj_ctx *c, int n) {
 // none: the batch's streams and events run their fills).
 static int create_fill_sync(ccj_ctx *c, size_t nev) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->st_copy, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->st_p, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->st_il, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->st_d, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->st_x, hipStreamNonBlocking));
-    // The cross-stream events only order work on this device, so they are recorded without the
-    // default system-scope fence (hipEventDisableSystemFence: fill -0.65 ms at n=200).
-    // ev_start / ev_end, which the host waits on, keep it.
-    constexpr unsigned fence_fl = (unsigned)hipEventDisableSystemFence;
-    const unsigned sync_fl = hipEventDisableTiming | fence_fl;
-    c->il_done.resize(nev);
-    for (auto &e : c->il_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
-    c->dg_done.resize(nev);
-    for (auto &e : c->dg_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
-    HIPCHK(c, hipEventCreate(&c->ev_start));
-    HIPCHK(c, hipEventCreate(&c->ev_end));
-    HIPCHK(c, hipEventCreate(&c->ev_pre));
-    c->lev_done.resize(nev);
-    // timed: the level durations (mode 1; recording them untimed measured the same)
-    for (auto &e : c->lev_done) HIPCHK(c, hipEventCreateWithFlags(&e, fence_fl));
-    c->p_done.resize(nev);
-    for (auto &e : c->p_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
-    c->pp_done.resize(nev);
-    for (auto &e : c->pp_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
-    c->bulk_done.resize(nev);
-    for (auto &e : c->bulk_done) HIPCHK(c, hipEventCreateWithFlags(&e, sync_fl));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_bpacked, sync_fl));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_bcopied, sync_fl));
+    HIPCHK(c, fill_sync_create(c->fs, nev, true));
+    if (c->exchanges()) {
+        Exchange &x = c->xch;
+        HIPCHK(c, hipStreamCreateWithFlags(&x.st_d, hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(&x.st_x, hipStreamNonBlocking));
+        for (auto *v : {&x.pp_done, &x.bulk_done}) {
+            v->assign(nev, nullptr);
+            for (auto &e : *v) HIPCHK(c, hipEventCreateWithFlags(&e, EV_ORDER));
+        }
+        HIPCHK(c, hipEventCreateWithFlags(&x.ev_bpacked, EV_ORDER));
+        HIPCHK(c, hipEventCreateWithFlags(&x.ev_bcopied, EV_ORDER));
+    }
     c->tev.resize(TEV_PER * nev);
     for (auto &e : c->tev) HIPCHK(c, hipEventCreate(&e));
     return CCJ_OK;
@@ -1043,10 +1075,6 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
         if (opts && opts->split_target) c->split_target = opts->split_target < 0 ? 0 : opts->split_target;
         const char *lt = getenv("CCJ_LEVEL_TIMING");
         if (lt) c->level_timing = std::max(0, std::min(2, atoi(lt)));
-        // k_diag2d(t-1) behind k_iloop(t) on one side stream, so each level waits on one event
-        // (fill -0.25 ms at n=200 in 3/3 alternating runs); band-sharded fills with an exchange
-        // partition each span instead, and the level-t exchange carries span t
-        c->join_diag = !(c->world > 1 && !c->simulate);
         const char *g = getenv("CCJ_SHARE_SPLITS");
         c->share = !(g && atoi(g) < 0) && !(opts && opts->share_splits < 0);
     }
@@ -1082,7 +1110,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
     // where the band-sharded exchange packs them or a host mirror streams them during the fill
     // (ccj_engine.h carrier); CCJ_D4_FULL=1 makes any context full (A/B timing).  The host mirror
     // always has 22
-    c->full4 = (c->world > 1 && !c->simulate) || c->overlap || (getenv("CCJ_D4_FULL") && atoi(getenv("CCJ_D4_FULL")) != 0);
+    c->full4 = c->exchanges() || c->overlap || (getenv("CCJ_D4_FULL") && atoi(getenv("CCJ_D4_FULL")) != 0);
     c->nm4 = c->full4 ? NMAT4 : NMAT_D4;
     // every allocation below is sized from the capacity's extents and nothing else
     c->cap_ext = layout_extents(nmax, c->world, c->nm4, c->split_target, c->share, true);
@@ -1124,7 +1152,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
     HIPCHK(cp, hipMalloc(&c->d_pair, 64));
     HIPCHK(cp, hipMalloc(&c->d_rtype, 8));
     HIPCHK(cp, hipMalloc(&c->d_lx, c->lx.size() * sizeof(int)));
-    HIPCHK(cp, hipMalloc(&c->d_err, 2 * sizeof(int)));  // the error word; [1]: the sharded range word (fill_enqueue)
+    HIPCHK(cp, hipMalloc(&c->d_err, 2 * sizeof(int)));  // the error word; [1]: the sharded range word (exchange_enqueue)
     HIPCHK(cp, hipMalloc(&c->d_S, (nmax + 2) * sizeof(short)));
     HIPCHK(cp, hipMalloc(&c->d_S1, (nmax + 2) * sizeof(short)));
     HIPCHK(cp, hipMalloc(&c->d_prm, sizeof(ccj_energy_params)));
@@ -1237,19 +1265,19 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
             c->items_cap = bound;
             HIPCHK(cp, hipMalloc(&c->d_items, c->items_cap * sizeof(uint32_t)));
         }
-        if (G > 1 && !c->simulate) {
+        if (c->exchanges()) {
             // exchange slices, per part: 22 matrices x the largest rank's blocks of the
             // part x M, then the part's tail (a band-sharded context holds one length: nmax == n)
             for (int part = 0; part < 2; ++part) {
-                c->xnmax[part].assign(n, 0);
+                c->xch.xnmax[part].assign(n, 0);
                 size_t slice = 0;
                 for (int t = 0; t + 2 < n; ++t) {
                     const int nm = xch_nmax(t, G, part), m = n - t - 2;
-                    c->xnmax[part][t] = nm;
+                    c->xch.xnmax[part][t] = nm;
                     slice = std::max(slice, (size_t)xch_slice(n, nm, m * (m + 1) / 2, part));
                 }
-                if (hipMalloc(&c->d_send[part], std::max<size_t>(slice, 1) * sizeof(int16_t)) != hipSuccess ||
-                    hipMalloc(&c->d_recv[part], std::max<size_t>(slice * G, 1) * sizeof(int16_t)) != hipSuccess)
+                if (hipMalloc(&c->xch.d_send[part], std::max<size_t>(slice, 1) * sizeof(int16_t)) != hipSuccess ||
+                    hipMalloc(&c->xch.d_recv[part], std::max<size_t>(slice * G, 1) * sizeof(int16_t)) != hipSuccess)
                     return set_err(cp, CCJ_E_OOM, "device allocation of the exchange buffers (%.2f GB) failed",
                                    slice * (G + 1) * 2e-9);
             }
@@ -1320,19 +1348,113 @@ extern "C" int ccj_rebind(ccj_ctx *c, const char *seq) { return rebind_impl(c, s
 extern "C" int ccj_capacity(const ccj_ctx *c) { return c ? c->ncap : 0; }
 
 
-// Enqueue the whole fill on the context's streams; it ends with ev_end on st, after which every
-// stream's work of the fill is complete (st waits for the last span, which waits for the last P,
-// and every level waited for its k_iloop / leader launches).
-// The P terms that complete P(lev+3): every term whose operands' highest level is lev (k_ppush,
-// DESIGN.md §4).  Band-sharded, each rank pushes its share (outer index r, r+G, ...; every share in
-// simulation) and the spans are min-combined in the exchange of level lev+1.
-static int pterm_launch(const ccj_ctx *c, int lev, hipStream_t s) {
-    for (int r = 0; r < c->world; ++r) {
-        if (!c->simulate && r != c->rank) continue;
-        if (const int e = ccjk_ppush(&c->T, lev, c->world, r, s)) return e;
+// The joined level graph of a fill, written once: every wait and record of the
+// four-stream wavefront over `steps` spans of which the first `nlev` are 4-D levels.
+//   st_il: k_iloop(t)   needs 4-D levels <= t-3 (lev_done[t-3]; the dt = 2 term is in k_level4d);
+//          k_diag2d(t-1) follows it on the same stream, behind P(t-1) (p_done), so that level t
+//          waits on one event that covers both (fill -0.25 ms at n=200 in 3/3 alternating runs)
+//   st   : k_level4d(t) needs level t-1 (stream order), k_iloop(t), k_diag2d(t-1)
+//   st_p : k_ppush(t)   needs level t (lev_done[t]); it completes P(t+3)
+// so k_diag2d(t) and k_iloop(t+1) overlap k_level4d(t).  Every event is recorded (enqueued) before
+// a stream waits on it.  What is launched is the launcher's affair (CtxLaunch, BatchLaunch):
+// L.pre(q), L.iloop(s, q), L.diag(sg, q), L.level(s, q), L.ppush(s, q) and L.behind_span(sg, q),
+// which follows span sg on its stream, in front of dg_done[sg].  It serves the unsharded fill, the
+// shard_simulate fill and the lockstep batch; the fill with an exchange has other edges
+// (exchange_enqueue).  The caller joins: the fill ends behind dg_done[steps-1].
+template <class Launch>
+static hipError_t enqueue_level_dag(const FillSync &f, hipStream_t st, int steps, int nlev, const Launch &L) {
+    HIPTRY(L.pre(st));
+    HIPTRY(hipEventRecord(f.ev_pre, st));
+    HIPTRY(hipStreamWaitEvent(f.st_il, f.ev_pre, 0));
+    HIPTRY(hipStreamWaitEvent(f.st_p, f.ev_pre, 0));
+    auto diag = [&](int sg) -> hipError_t {
+        if (sg >= 3) HIPTRY(hipStreamWaitEvent(f.st_il, f.p_done[sg], 0));
+        HIPTRY(L.diag(sg, f.st_il));
+        HIPTRY(L.behind_span(sg, f.st_il));
+        return hipEventRecord(f.dg_done[sg], f.st_il);
+    };
+    for (int s = 0; s < steps; ++s) {
+        if (s >= nlev) {  // the spans past the last level; the first of them still owes span nlev-1
+            if (s == nlev && s >= 1) HIPTRY(diag(s - 1));
+            HIPTRY(diag(s));
+            continue;
+        }
+        if (s >= 3) HIPTRY(hipStreamWaitEvent(f.st_il, f.lev_done[s - 3], 0));
+        HIPTRY(L.iloop(s, f.st_il));
+        if (s >= 1) HIPTRY(diag(s - 1));
+        HIPTRY(hipEventRecord(f.il_done[s], f.st_il));
+        HIPTRY(hipStreamWaitEvent(st, f.il_done[s], 0));
+        HIPTRY(L.level(s, st));
+        HIPTRY(hipEventRecord(f.lev_done[s], st));
+        if (s + 3 < steps) {  // P(s+3) only needs PK levels <= s
+            HIPTRY(hipStreamWaitEvent(f.st_p, f.lev_done[s], 0));
+            HIPTRY(L.ppush(s, f.st_p));
+            HIPTRY(hipEventRecord(f.p_done[s + 3], f.st_p));
+        }
     }
-    return 0;
+    return hipSuccess;
 }
+
+// A context's launches: ccjk_* for each rank the context launches for, and in timing mode 2 the
+// markers tev[0..5, 7, 8] around them (TEV_PER).  Both of a context's graphs launch through it.
+struct CtxLaunch {
+    const ccj_ctx *c;
+    hipError_t mark(int s, int x, hipStream_t q) const {
+        return c->level_timing == 2 ? hipEventRecord(c->tev[TEV_PER * (size_t)s + x], q) : hipSuccess;
+    }
+    // every rank's launch in simulation, else this rank's (the only one when unsharded)
+    template <class F>
+    hipError_t ranks(F launch) const {
+        for (int r = 0; r < c->world; ++r)
+            if (c->simulate || r == c->rank) HIPTRY(launch(r));
+        return hipSuccess;
+    }
+    hipError_t pre(hipStream_t q) const {
+        HIPTRY(ccjk_init2d(&c->T, q));
+        HIPTRY(ccjk_precompute_ie(&c->T, q));
+        return (hipError_t)ccjk_build_il(&c->T, q);
+    }
+    hipError_t iloop(int s, hipStream_t q) const {
+        HIPTRY(mark(s, 2, q));
+        HIPTRY(ranks([&](int r) {
+            const size_t tr = (size_t)s * c->world + r;
+            return ccjk_iloop(&c->T, s, c->it_off[tr], (int)(c->it_off[tr + 1] - c->it_off[tr]), c->world, r, q);
+        }));
+        return mark(s, 3, q);
+    }
+    // span sg, its intervals partitioned over G ranks (G = 1: every interval)
+    hipError_t diag(int sg, int G, hipStream_t q) const {
+        HIPTRY(mark(sg, 0, q));
+        if (G == 1) HIPTRY(ccjk_diag2d(&c->T, sg, 1, 0, q));
+        else HIPTRY(ranks([&](int r) { return ccjk_diag2d(&c->T, sg, G, r, q); }));
+        return mark(sg, 1, q);
+    }
+    hipError_t diag(int sg, hipStream_t q) const { return diag(sg, c->world, q); }
+    // behind span n-3, the longest a valid cell's (i,j) or (k,l) can have: the range check of the six
+    // closed-form matrices (site CF; every rank holds the whole tables).  The two spans
+    // that follow on this stream are ordered behind it, so the fill's end (dg_done[n-1]) covers it,
+    // and it runs beside the last level.
+    hipError_t behind_span(int sg, hipStream_t q) const { return sg == c->n - 3 ? (hipError_t)ccjk_cf_low(&c->T, q) : hipSuccess; }
+    // the level: its plain launch, then (sharing levels) the leaders on the same stream, no
+    // cross-stream hop between the two launches or between levels
+    hipError_t level(int s, hipStream_t q) const {
+        HIPTRY(mark(s, 4, q));
+        HIPTRY(level_launches(s, q));
+        return mark(s, 5, q);
+    }
+    hipError_t level_launches(int s, hipStream_t q) const {
+        HIPTRY(ranks([&](int r) { return ccjk_level4d(&c->T, s, c->world, r, 1, q); }));
+        return ranks([&](int r) { return ccjk_level4d_lead(&c->T, s, c->world, r, q); });
+    }
+    // The P terms that complete P(s+3): every term whose operands' highest level is s (k_ppush,
+    // DESIGN.md §4).  Band-sharded, each rank pushes its share (outer index r, r+G, ...; every share
+    // in simulation) and the spans are min-combined in the exchange of level s+1.
+    hipError_t ppush(int s, hipStream_t q) const {
+        HIPTRY(mark(s, 7, q));
+        HIPTRY(ranks([&](int r) { return ccjk_ppush(&c->T, s, c->world, r, q); }));
+        return mark(s, 8, q);
+    }
+};
 
 // A full context's d4 has the host mirror's layout except that the fill leaves the IN_TAB and IN_CF
 // slots (the last twelve) of every level unwritten: write level t's from the tables, in front of a
@@ -1342,230 +1464,183 @@ static int expand_tab_slots(const ccj_ctx *c, int t, hipStream_t s) {
     return ccjk_expand(&c->T, t, first, c->d4 + c->lv_off[t] + (size_t)first * c->lv_host[t].C, s);
 }
 
+// The level graph of the band-sharded fill with an exchange (in-process group or
+// RCCL).  Its edges differ from the joined graph's: each span is partitioned by rank and runs on
+// st_d, the level-s edge exchange on the level stream carries span s and the partials of P(s+1), and
+// the bulk exchange runs one level behind on st_x.
+//   st_d : k_diag2d(s)  needs P(s) (p_done) and span s-1 from the other ranks (lev_done[s-1])
+//   st_il: k_iloop(t)   needs levels <= t-3 complete on this rank (bulk_done[t-3])
+//   st   : k_level4d(t) needs level t-1 (stream order), k_iloop(t), k_diag2d(t-1), and the other
+//                       ranks' blocks of level t-2 (bulk_done[t-2]); then the edge exchange
+//   st_p : k_ppush(t)   needs level t complete (bulk_done[t]); records pp_done[t+3], and the edge
+//                       exchange that combines the ranks' partials records p_done
+//   st_x : the bulk exchange of level t, behind lev_done[t]; records bulk_done[t]
+// Timing mode 2 adds the markers 6 (the edge exchange's start) and 9, 10 (the bulk exchange).
+static int exchange_enqueue(ccj_ctx *c) {
+    const int n = c->n, G = c->world, nlev = c->nlev;
+    const FillSync &f = c->fs;
+    Exchange &x = c->xch;
+    const CtxLaunch L{c};
+    hipStream_t st = c->st;
+    HIPCHK(c, L.pre(st));
+    HIPCHK(c, hipEventRecord(f.ev_pre, st));
+    HIPCHK(c, hipStreamWaitEvent(x.st_d, f.ev_pre, 0));
+    HIPCHK(c, hipStreamWaitEvent(f.st_il, f.ev_pre, 0));
+    HIPCHK(c, hipStreamWaitEvent(f.st_p, f.ev_pre, 0));
+    // Exchange of level s, part `part` (ccj_engine.h XCH_EDGE / XCH_BULK): pack the rank's blocks of the
+    // part (+ the part's tail), gather, unpack.  The edge part runs on the level stream; the bulk part on
+    // st_x, split into its start (wait, pack; over RCCL also gather and unpack) and, for the in-process
+    // group, its finish one level later (the host-side gather), so that the host thread does not block
+    // on it before the next level is enqueued.
+    auto part_slice = [&](int s, int part) { return (size_t)xch_slice(n, x.xnmax[part][s], c->lv_host[s].M, part); };
+    auto gather = [&](int part, size_t slice, hipStream_t q, const char *what, int s) -> int {
+        if (x.lgroup) return local_allgather(c, part, slice, q);
+        ncclComm_t cm = part == XCH_EDGE ? x.comm : x.comm_b;
+        if (!cm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
+        if (ncclAllGather(x.d_send[part], x.d_recv[part], slice * sizeof(int16_t), ncclInt8, cm, q) != ncclSuccess)
+            return set_err(c, CCJ_E_COMM, "ncclAllGather (%s) failed at level %d", what, s);
+        return CCJ_OK;
+    };
+    auto bulk_unpack = [&](int s) -> int {
+        HIPCHK(c, (hipError_t)ccjk_unpack(&c->T, s, G, c->rank, XCH_BULK, x.xnmax[XCH_BULK][s], x.d_recv[XCH_BULK],
+                                          part_slice(s, XCH_BULK), x.st_x));
+        HIPCHK(c, L.mark(s, 10, x.st_x));
+        HIPCHK(c, hipEventRecord(x.bulk_done[s], x.st_x));
+        return CCJ_OK;
+    };
+    auto bulk_start = [&](int s) -> int {
+        HIPCHK(c, hipStreamWaitEvent(x.st_x, f.lev_done[s], 0));
+        if (x.lgroup) {
+            if (const int rc = local_bulk_wait_copied(c)) return rc;
+        }
+        HIPCHK(c, L.mark(s, 9, x.st_x));
+        HIPCHK(c, (hipError_t)ccjk_pack(&c->T, s, G, c->rank, XCH_BULK, x.xnmax[XCH_BULK][s], x.d_send[XCH_BULK], x.st_x));
+        if (x.lgroup) {  // gathered and unpacked when the next level is enqueued (bulk_finish)
+            HIPCHK(c, hipEventRecord(x.ev_bpacked, x.st_x));
+            return CCJ_OK;
+        }
+        if (const int rc = gather(XCH_BULK, part_slice(s, XCH_BULK), x.st_x, "bulk", s)) return rc;
+        return bulk_unpack(s);
+    };
+    // the in-process group's bulk gather of level s, then what waits for level s to be complete on
+    // this rank: its share of the P terms of P(s+3), combined in the edge exchange of level s+2
+    auto bulk_finish = [&](int s) -> int {
+        if (x.lgroup) {
+            if (const int rc = local_bulk_gather(c, part_slice(s, XCH_BULK))) return rc;
+            if (const int rc = bulk_unpack(s)) return rc;
+        }
+        if (s + 3 < n) {
+            HIPCHK(c, hipStreamWaitEvent(f.st_p, x.bulk_done[s], 0));
+            HIPCHK(c, L.ppush(s, f.st_p));
+            HIPCHK(c, hipEventRecord(x.pp_done[s + 3], f.st_p));
+        }
+        return CCJ_OK;
+    };
+    for (int s = 0; s < n; ++s) {
+        // span s: this rank's intervals (the exchange of level s brings the rest); past the last
+        // level no exchange is left, so every rank computes every interval
+        if (s >= 3) HIPCHK(c, hipStreamWaitEvent(x.st_d, f.p_done[s], 0));
+        // span s-1 is complete on this rank only after the level-(s-1) edge exchange, which carries it
+        if (s >= 1 && s - 1 < nlev) HIPCHK(c, hipStreamWaitEvent(x.st_d, f.lev_done[s - 1], 0));
+        HIPCHK(c, L.diag(s, s < nlev ? G : 1, x.st_d));
+        HIPCHK(c, L.behind_span(s, x.st_d));
+        HIPCHK(c, hipEventRecord(f.dg_done[s], x.st_d));
+        if (s >= nlev) {
+            if (s > nlev) continue;
+            if (s >= 1) {  // the last level's bulk part
+                if (const int rc = bulk_finish(s - 1)) return rc;
+            }
+            if (n - 1 >= 3) {
+                // the partials of P(n-1) (pushed after level n-4): no level n-2 carries them, so they
+                // travel alone, as a slice of one P tail in the edge buffers
+                const int sig = n - 1;
+                const size_t pslice = (size_t)xch_ptail(n);
+                HIPCHK(c, hipStreamWaitEvent(st, x.pp_done[sig], 0));
+                HIPCHK(c, (hipError_t)ccjk_ptail_pack(&c->T, sig, x.d_send[XCH_EDGE], st));
+                if (const int rc = gather(XCH_EDGE, pslice, st, "P tail", s)) return rc;
+                HIPCHK(c, (hipError_t)ccjk_ptail_unpack(&c->T, sig, x.d_recv[XCH_EDGE], pslice, 0, G, st));
+                HIPCHK(c, hipEventRecord(f.p_done[sig], st));
+            }
+            continue;
+        }
+        // k_iloop(s) reads levels <= s-3 (complete: their bulk parts unpacked)
+        if (s >= 3) HIPCHK(c, hipStreamWaitEvent(f.st_il, x.bulk_done[s - 3], 0));
+        HIPCHK(c, L.iloop(s, f.st_il));
+        HIPCHK(c, hipEventRecord(f.il_done[s], f.st_il));
+        HIPCHK(c, hipStreamWaitEvent(st, f.il_done[s], 0));
+        if (s >= 1) HIPCHK(c, hipStreamWaitEvent(st, f.dg_done[s - 1], 0));
+        // level s reads the other ranks' blocks of level s-2 from its bulk part (the edge part of
+        // level s-1 arrived on this stream; older levels precede s-2 on st_x)
+        if (s >= 2) HIPCHK(c, hipStreamWaitEvent(st, x.bulk_done[s - 2], 0));
+        HIPCHK(c, L.mark(s, 4, st));
+        HIPCHK(c, L.level_launches(s, st));
+        // the previous level's bulk part (in-process: its gather), the P terms it completes
+        if (s >= 1) {
+            if (const int rc = bulk_finish(s - 1)) return rc;
+        }
+        HIPCHK(c, L.mark(s, 6, st));  // timing mode 2: the edge exchange's share of the level span
+        // edge part: the rank's blocks a % 4 == 3 (all 22 matrices), its partials of P(s+1)
+        // (pushed after level s-2, so a level of slack) and its intervals of span s
+        const size_t slice = part_slice(s, XCH_EDGE), body = (size_t)xch_body(x.xnmax[XCH_EDGE][s], c->lv_host[s].M);
+        const size_t dt_off = body + (size_t)xch_ptail(n);
+        const int sig = s + 1;
+        const bool ptail = sig >= 3 && sig <= n - 2;
+        if (ptail) {
+            HIPCHK(c, hipStreamWaitEvent(st, x.pp_done[sig], 0));
+            HIPCHK(c, (hipError_t)ccjk_ptail_pack(&c->T, sig, x.d_send[XCH_EDGE] + body, st));
+        }
+        HIPCHK(c, hipStreamWaitEvent(st, f.dg_done[s], 0));
+        HIPCHK(c, (hipError_t)ccjk_dtail_pack(&c->T, s, G, c->rank, x.d_send[XCH_EDGE] + dt_off, st));
+        HIPCHK(c, (hipError_t)ccjk_pack(&c->T, s, G, c->rank, XCH_EDGE, x.xnmax[XCH_EDGE][s], x.d_send[XCH_EDGE], st));
+        if (const int rc = gather(XCH_EDGE, slice, st, "edge", s)) return rc;
+        HIPCHK(c, (hipError_t)ccjk_unpack(&c->T, s, G, c->rank, XCH_EDGE, x.xnmax[XCH_EDGE][s], x.d_recv[XCH_EDGE], slice, st));
+        HIPCHK(c, (hipError_t)ccjk_dtail_unpack(&c->T, s, x.d_recv[XCH_EDGE], slice, dt_off, G, c->rank, st));
+        if (ptail) {
+            HIPCHK(c, (hipError_t)ccjk_ptail_unpack(&c->T, sig, x.d_recv[XCH_EDGE], slice, body, G, st));
+            HIPCHK(c, hipEventRecord(f.p_done[sig], st));  // P(sig) final on every rank
+        }
+        HIPCHK(c, L.mark(s, 5, st));
+        HIPCHK(c, hipEventRecord(f.lev_done[s], st));
+        if (const int rc = bulk_start(s)) return rc;
+    }
+    // over RCCL a rank sees the LEVEL / ILOOP / PARTIAL sites of its own blocks only, so after the
+    // last level the ranks sum one 4-byte word of per-site counts on the level stream's communicator
+    // and every rank ends with the union (the in-process group: fill_finish)
+    if (!x.lgroup) {
+        if (!x.comm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
+        unsigned *word = (unsigned *)(c->d_err + 1);
+        HIPCHK(c, (hipError_t)ccjk_range_spread(&c->T, word, st));
+        if (ncclAllReduce(word, word, 1, ncclUint32, ncclSum, x.comm, st) != ncclSuccess)
+            return set_err(c, CCJ_E_COMM, "ncclAllReduce (range sites) failed");
+        HIPCHK(c, (hipError_t)ccjk_range_merge(&c->T, word, st));
+    }
+    // the fill's end also covers every rank's part of the last level
+    if (nlev >= 1) HIPCHK(c, hipStreamWaitEvent(st, x.bulk_done[nlev - 1], 0));
+    return CCJ_OK;
+}
+
+// Enqueue the whole fill on the context's streams; it ends with ev_end on st, after which every
+// stream's work of the fill is complete (st waits for the last span, which waits for the last P,
+// and every level waited for its k_iloop / leader launches).
 static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     if (!c) return CCJ_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->n;
+    const FillSync &f = c->fs;
     hipStream_t st = c->st;
     // pipelining (ccj_fill_async_after): start when the other context's last enqueued fill has
     // ended (its ev_end; its W + traceback may still run beside this fill)
-    if (after && after != c && after->ev_end) HIPCHK(c, hipStreamWaitEvent(st, after->ev_end, 0));
+    if (after && after != c && after->fs.ev_end) HIPCHK(c, hipStreamWaitEvent(st, after->fs.ev_end, 0));
     const auto enq0 = std::chrono::steady_clock::now();
     c->filled = c->mirrored = c->mirrored2d = false;
     c->range_flags = 0;
     c->range_refused = false;
     HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), st));
-    HIPCHK(c, hipEventRecord(c->ev_start, st));
-    HIPCHK(c, (hipError_t)ccjk_init2d(&c->T, st));
-    HIPCHK(c, (hipError_t)ccjk_precompute_ie(&c->T, st));
-    HIPCHK(c, (hipError_t)ccjk_build_il(&c->T, st));
-    HIPCHK(c, hipEventRecord(c->ev_pre, st));
-    // Four streams:
-    //   st_d : k_diag2d(s)  needs P(s) (p_done) and spans < s (stream order); with join_diag (below)
-    //                       it runs on st_il instead, behind k_iloop(s+1), and st_d stays empty
-    //   st_il: k_iloop(t)   needs 4-D levels <= t-3 (lev_done[t-3]; the dt = 2 term is in k_level4d)
-    //   st   : k_level4d(t) needs level t-1 (stream order), k_iloop(t), k_diag2d(t-1)
-    //   st_p : k_pterm(s)   needs PK levels <= s-3 (lev_done[s-3])
-    // so k_diag2d(t) and k_iloop(t+1) overlap k_level4d(t).  Every event is recorded (enqueued)
-    // before a stream waits on it.
-    HIPCHK(c, hipStreamWaitEvent(c->st_d, c->ev_pre, 0));
-    HIPCHK(c, hipStreamWaitEvent(c->st_il, c->ev_pre, 0));
-    HIPCHK(c, hipStreamWaitEvent(c->st_p, c->ev_pre, 0));
-    const bool xchg = c->world > 1 && !c->simulate;
-    // level t complete on this rank: its lev_done, or, band-sharded, when the bulk part of its
-    // exchange is unpacked (bulk_done[t]; lev_done[t] then only covers the rank's own cells and the
-    // other ranks' edge blocks, which is all level t+1 reads of level t)
-    const std::vector<hipEvent_t> &lvl_full = xchg ? c->bulk_done : c->lev_done;
-    // what follows a level's completion on this rank: the P terms pushed by it
-    auto after_level = [&](int s) -> int {
-        // P(s+3) only needs PK levels <= s; band-sharded, this rank's partials are combined in the
-        // bulk exchange of level s+1, which then records p_done[s+3]
-        if (s + 3 < n) {
-            hipEvent_t *ev = &c->tev[TEV_PER * (size_t)s];
-            HIPCHK(c, hipStreamWaitEvent(c->st_p, lvl_full[s], 0));
-            if (c->level_timing == 2) HIPCHK(c, hipEventRecord(ev[7], c->st_p));
-            HIPCHK(c, (hipError_t)pterm_launch(c, s, c->st_p));
-            if (c->level_timing == 2) HIPCHK(c, hipEventRecord(ev[8], c->st_p));
-            HIPCHK(c, hipEventRecord((xchg ? c->pp_done : c->p_done)[s + 3], c->st_p));
-        }
-        return CCJ_OK;
-    };
-    // Band-sharded exchange of level s, part `part` (ccj_engine.h XCH_EDGE / XCH_BULK):
-    // pack the rank's blocks of the part (+ the part's tail), gather, unpack.  The edge part runs on the
-    // level stream; the bulk part on st_x, split into its start (wait, pack; over RCCL also gather and
-    // unpack) and, for the in-process group, its finish one level later (the host-side gather), so
-    // that the host thread does not block on it before the next level is enqueued.
-    auto part_slice = [&](int s, int part) { return (size_t)xch_slice(n, c->xnmax[part][s], c->lv_host[s].M, part); };
-    auto part_body = [&](int s, int part) { return (size_t)xch_body(c->xnmax[part][s], c->lv_host[s].M); };
-    auto gather = [&](int s, int part, hipStream_t q) -> int {
-        if (c->lgroup) return local_allgather(c, part, part_slice(s, part), q);
-        ncclComm_t cm = part == XCH_EDGE ? c->comm : c->comm_b;
-        if (!cm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
-        if (ncclAllGather(c->d_send[part], c->d_recv[part], part_slice(s, part) * sizeof(int16_t), ncclInt8, cm, q) != ncclSuccess)
-            return set_err(c, CCJ_E_COMM, "ncclAllGather (%s) failed at level %d", part == XCH_EDGE ? "edge" : "bulk", s);
-        return CCJ_OK;
-    };
-    auto bulk_unpack = [&](int s) -> int {
-        hipEvent_t *ev = &c->tev[TEV_PER * (size_t)s];
-        HIPCHK(c, (hipError_t)ccjk_unpack(&c->T, s, c->world, c->rank, XCH_BULK, c->xnmax[XCH_BULK][s], c->d_recv[XCH_BULK],
-                                          part_slice(s, XCH_BULK), c->st_x));
-        if (c->level_timing == 2) HIPCHK(c, hipEventRecord(ev[10], c->st_x));
-        HIPCHK(c, hipEventRecord(c->bulk_done[s], c->st_x));
-        return CCJ_OK;
-    };
-    auto bulk_start = [&](int s) -> int {
-        hipEvent_t *ev = &c->tev[TEV_PER * (size_t)s];
-        HIPCHK(c, hipStreamWaitEvent(c->st_x, c->lev_done[s], 0));
-        if (c->lgroup) {
-            if (const int rc = local_bulk_wait_copied(c)) return rc;
-        }
-        if (c->level_timing == 2) HIPCHK(c, hipEventRecord(ev[9], c->st_x));
-        HIPCHK(c, (hipError_t)ccjk_pack(&c->T, s, c->world, c->rank, XCH_BULK, c->xnmax[XCH_BULK][s], c->d_send[XCH_BULK], c->st_x));
-        if (c->lgroup) {  // gathered and unpacked when the next level is enqueued (bulk_finish)
-            HIPCHK(c, hipEventRecord(c->ev_bpacked, c->st_x));
-            return CCJ_OK;
-        }
-        if (const int rc = gather(s, XCH_BULK, c->st_x)) return rc;
-        return bulk_unpack(s);
-    };
-    // the in-process group's bulk gather of level s, then what waits for level s to be complete
-    auto bulk_finish = [&](int s) -> int {
-        if (c->lgroup) {
-            if (const int rc = local_bulk_gather(c, part_slice(s, XCH_BULK))) return rc;
-            if (const int rc = bulk_unpack(s)) return rc;
-        }
-        return after_level(s);
-    };
-    for (int s = 0; s < n; ++s) {
-        hipEvent_t *ev = &c->tev[TEV_PER * (size_t)s];
-        // timing markers (ev[0..10]) only when per-kernel timing is on
-        auto trec = [&](int x, hipStream_t q) { return c->level_timing == 2 ? hipEventRecord(ev[x], q) : hipSuccess; };
-        // k_diag2d(sigma) on st_d; or, joined (c->join_diag), on st_il right after k_iloop(sigma+1),
-        // so that level sigma+1 waits on one event that covers both
-        auto enqueue_diag = [&](int sg, hipStream_t q) -> int {
-            hipEvent_t *evd = &c->tev[TEV_PER * (size_t)sg];
-            if (sg >= 3) HIPCHK(c, hipStreamWaitEvent(q, c->p_done[sg], 0));
-            // band-sharded: span sg-1 is complete on this rank only after the level-(sg-1) edge
-            // exchange, which carries it
-            if (xchg && sg >= 1 && sg - 1 < c->nlev) HIPCHK(c, hipStreamWaitEvent(q, c->lev_done[sg - 1], 0));
-            if (c->level_timing == 2) HIPCHK(c, hipEventRecord(evd[0], q));
-            if (c->simulate) {  // every rank's share of the span, in one context
-                for (int r = 0; r < c->world; ++r) HIPCHK(c, (hipError_t)ccjk_diag2d(&c->T, sg, c->world, r, q));
-            } else if (xchg && sg < c->nlev) {  // this rank's intervals; the exchange of level sg brings the rest
-                HIPCHK(c, (hipError_t)ccjk_diag2d(&c->T, sg, c->world, c->rank, q));
-            } else {  // unsharded, or the spans past the last 4-D level (no exchange left): every interval
-                HIPCHK(c, (hipError_t)ccjk_diag2d(&c->T, sg, 1, 0, q));
-            }
-            if (c->level_timing == 2) HIPCHK(c, hipEventRecord(evd[1], q));
-            // behind span n-3, the longest a valid cell's (i,j) or (k,l) can have, on its stream: the
-            // range check of the six closed-form matrices (site CF; every rank holds the
-            // whole tables).  The two spans that follow on this stream are ordered behind it, so the
-            // fill's end (dg_done[n-1]) covers it, and it runs beside the last level.
-            if (sg == n - 3) HIPCHK(c, (hipError_t)ccjk_cf_low(&c->T, q));
-            HIPCHK(c, hipEventRecord(c->dg_done[sg], q));
-            return CCJ_OK;
-        };
-        const bool joined = c->join_diag && s >= 1 && s < c->nlev;  // diag(s-1) follows iloop(s)
-        if (!c->join_diag || s >= c->nlev) {
-            if (c->join_diag && s == c->nlev && s >= 1 && s - 1 < c->nlev) {
-                if (const int rc = enqueue_diag(s - 1, c->st_il)) return rc;  // last one behind iloop
-            }
-            if (const int rc = enqueue_diag(s, c->join_diag ? c->st_il : c->st_d)) return rc;
-        }
-        if (s < c->nlev) {
-            // k_iloop(s) reads levels <= s-3 (complete: band-sharded, their bulk parts unpacked)
-            if (s >= 3) HIPCHK(c, hipStreamWaitEvent(c->st_il, lvl_full[s - 3], 0));
-            HIPCHK(c, trec(2, c->st_il));
-            const int G = c->world;
-            for (int r = 0; r < G; ++r) {  // every rank's launches in simulation, else this rank's
-                if (!c->simulate && r != c->rank) continue;
-                const size_t tr = (size_t)s * G + r;
-                HIPCHK(c, (hipError_t)ccjk_iloop(&c->T, s, c->it_off[tr], (int)(c->it_off[tr + 1] - c->it_off[tr]), G, r,
-                                                 c->st_il));
-            }
-            HIPCHK(c, trec(3, c->st_il));
-            if (joined) {
-                if (const int rc = enqueue_diag(s - 1, c->st_il)) return rc;
-            }
-            HIPCHK(c, hipEventRecord(c->il_done[s], c->st_il));
-            HIPCHK(c, hipStreamWaitEvent(st, c->il_done[s], 0));
-            if (s >= 1 && !c->join_diag) HIPCHK(c, hipStreamWaitEvent(st, c->dg_done[s - 1], 0));
-            // band-sharded: level s reads the other ranks' blocks of level s-2 from its bulk part (the
-            // edge part of level s-1 arrived on this stream; older levels precede s-2 on st_x)
-            if (xchg && s >= 2) HIPCHK(c, hipStreamWaitEvent(st, c->bulk_done[s - 2], 0));
-            HIPCHK(c, trec(4, st));
-            // the level: its plain launch, then (sharing levels) the leaders on the same stream, no
-            // cross-stream hop between the two launches or between levels
-            for (int r = 0; r < G; ++r) {
-                if (!c->simulate && r != c->rank) continue;
-                HIPCHK(c, (hipError_t)ccjk_level4d(&c->T, s, G, r, 1, st));
-            }
-            for (int r = 0; r < G; ++r) {
-                if (!c->simulate && r != c->rank) continue;
-                HIPCHK(c, (hipError_t)ccjk_level4d_lead(&c->T, s, G, r, st));
-            }
-            if (xchg) {
-                // the previous level's bulk part (in-process: its gather), the P terms it completes
-                if (s >= 1) {
-                    if (const int rc = bulk_finish(s - 1)) return rc;
-                }
-                HIPCHK(c, trec(6, st));  // timing mode 2: the edge exchange's share of the level span
-                // edge part: the rank's blocks a % 4 == 3 (all 22 matrices), its partials of P(s+1)
-                // (pushed after level s-2, so a level of slack) and its intervals of span s
-                const size_t body = part_body(s, XCH_EDGE), dt_off = body + (size_t)xch_ptail(n);
-                const int sig = s + 1;
-                const bool ptail = sig >= 3 && sig <= n - 2;
-                if (ptail) {
-                    HIPCHK(c, hipStreamWaitEvent(st, c->pp_done[sig], 0));
-                    HIPCHK(c, (hipError_t)ccjk_ptail_pack(&c->T, sig, c->d_send[XCH_EDGE] + body, st));
-                }
-                HIPCHK(c, hipStreamWaitEvent(st, c->dg_done[s], 0));
-                HIPCHK(c, (hipError_t)ccjk_dtail_pack(&c->T, s, G, c->rank, c->d_send[XCH_EDGE] + dt_off, st));
-                HIPCHK(c, (hipError_t)ccjk_pack(&c->T, s, G, c->rank, XCH_EDGE, c->xnmax[XCH_EDGE][s], c->d_send[XCH_EDGE], st));
-                if (const int rc = gather(s, XCH_EDGE, st)) return rc;
-                HIPCHK(c, (hipError_t)ccjk_unpack(&c->T, s, G, c->rank, XCH_EDGE, c->xnmax[XCH_EDGE][s], c->d_recv[XCH_EDGE],
-                                                  part_slice(s, XCH_EDGE), st));
-                HIPCHK(c, (hipError_t)ccjk_dtail_unpack(&c->T, s, c->d_recv[XCH_EDGE], part_slice(s, XCH_EDGE), dt_off, G, c->rank,
-                                                        st));
-                if (ptail) {
-                    HIPCHK(c, (hipError_t)ccjk_ptail_unpack(&c->T, sig, c->d_recv[XCH_EDGE], part_slice(s, XCH_EDGE), body, G, st));
-                    HIPCHK(c, hipEventRecord(c->p_done[sig], st));  // P(sig) final on every rank
-                }
-            }
-            HIPCHK(c, trec(5, st));
-            HIPCHK(c, hipEventRecord(c->lev_done[s], st));
-            if (xchg) {
-                if (const int rc = bulk_start(s)) return rc;
-            } else if (const int rc = after_level(s)) {
-                return rc;
-            }
-        } else {
-            if (xchg && s == c->nlev && s >= 1) {  // the last level's bulk part
-                if (const int rc = bulk_finish(s - 1)) return rc;
-            }
-            if (xchg && s == c->nlev && n - 1 >= 3) {
-                // the partials of P(n-1) (pushed after level n-4): no level n-2 carries them, so they
-                // travel alone, as a slice of one P tail in the edge buffers
-                const int sig = n - 1;
-                const size_t pslice = (size_t)xch_ptail(n);
-                HIPCHK(c, hipStreamWaitEvent(st, c->pp_done[sig], 0));
-                HIPCHK(c, (hipError_t)ccjk_ptail_pack(&c->T, sig, c->d_send[XCH_EDGE], st));
-                if (c->lgroup) {
-                    if (const int rc = local_allgather(c, XCH_EDGE, pslice, st)) return rc;
-                } else {
-                    if (!c->comm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
-                    if (ncclAllGather(c->d_send[XCH_EDGE], c->d_recv[XCH_EDGE], pslice * sizeof(int16_t), ncclInt8, c->comm, st) !=
-                        ncclSuccess)
-                        return set_err(c, CCJ_E_COMM, "ncclAllGather (P tail) failed");
-                }
-                HIPCHK(c, (hipError_t)ccjk_ptail_unpack(&c->T, sig, c->d_recv[XCH_EDGE], pslice, 0, c->world, st));
-                HIPCHK(c, hipEventRecord(c->p_done[sig], st));
-            }
-            if (s + 3 < n && s + 3 >= 3) {
-                HIPCHK(c, (hipError_t)pterm_launch(c, s, c->st_p));
-                HIPCHK(c, hipEventRecord(c->p_done[s + 3], c->st_p));
-            }
-        }
+    HIPCHK(c, hipEventRecord(f.ev_start, st));
+    if (c->exchanges()) {
+        if (const int rc = exchange_enqueue(c)) return rc;
+    } else {
+        HIPCHK(c, enqueue_level_dag(f, st, n, c->nlev, CtxLaunch{c}));
     }
     if (getenv("CCJ_TRACE_ENQUEUE"))
         fprintf(stderr, "ccj_fill_device: enqueue %.2f ms\n",
@@ -1573,30 +1648,21 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
     if (c->overlap && c->h4) {
         // stream each finished level to the pinned host mirror while later levels run.  Its six
         // table-carried slots are written first, from table spans <= s (k_diag2d(s)); enqueued here
-        // because every event st_copy waits on must have been recorded
+        // because every event st_copy waits on must have been recorded.  Level s is complete on this
+        // rank at its lev_done or, with an exchange, when its bulk part is unpacked (lev_done[s] then
+        // only covers the rank's own cells and the other ranks' edge blocks)
+        const std::vector<hipEvent_t> &complete = c->exchanges() ? c->xch.bulk_done : f.lev_done;
         for (int s = 0; s < c->nlev; ++s) {
-            HIPCHK(c, hipStreamWaitEvent(c->st_copy, lvl_full[s], 0));
-            HIPCHK(c, hipStreamWaitEvent(c->st_copy, c->dg_done[s], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->st_copy, complete[s], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->st_copy, f.dg_done[s], 0));
             HIPCHK(c, (hipError_t)expand_tab_slots(c, s, c->st_copy));
             const size_t bytes = (size_t)NMAT4 * c->lv_host[s].C * sizeof(int16_t);
             HIPCHK(c, hipMemcpyAsync(c->h4 + c->lv_offh[s], c->d4 + c->lv_off[s], bytes, hipMemcpyDeviceToHost, c->st_copy));
         }
     }
-    // band-sharded over RCCL: a rank sees the LEVEL / ILOOP / PARTIAL sites of its own blocks only, so
-    // after the last level the ranks sum one 4-byte word of per-site counts on the level stream's
-    // communicator and every rank ends with the union (the in-process group: fill_finish)
-    if (xchg && !c->lgroup) {
-        if (!c->comm) return set_err(c, CCJ_E_STATE, "sharded context without ccj_comm_init");
-        unsigned *word = (unsigned *)(c->d_err + 1);
-        HIPCHK(c, (hipError_t)ccjk_range_spread(&c->T, word, st));
-        if (ncclAllReduce(word, word, 1, ncclUint32, ncclSum, c->comm, st) != ncclSuccess)
-            return set_err(c, CCJ_E_COMM, "ncclAllReduce (range sites) failed");
-        HIPCHK(c, (hipError_t)ccjk_range_merge(&c->T, word, st));
-    }
-    // join: the fill ends when the last level (every rank's part of it) and the last span are done
-    HIPCHK(c, hipStreamWaitEvent(st, c->dg_done[n - 1], 0));
-    if (xchg && c->nlev >= 1) HIPCHK(c, hipStreamWaitEvent(st, c->bulk_done[c->nlev - 1], 0));
-    HIPCHK(c, hipEventRecord(c->ev_end, st));
+    // join: the fill ends when the last level and the last span are done
+    HIPCHK(c, hipStreamWaitEvent(st, f.dg_done[n - 1], 0));
+    HIPCHK(c, hipEventRecord(f.ev_end, st));
     c->pending = true;
     return CCJ_OK;
 }
@@ -1606,8 +1672,8 @@ static int fill_enqueue(ccj_ctx *c, const ccj_ctx *after = nullptr) {
 // state and a deadline (CCJ_COMM_TIMEOUT_S, default 300 s) and, on either, aborts the communicator
 // (ncclCommAbort makes the pending collectives return) and fails with CCJ_E_COMM instead of hanging.
 static int wait_fill_end(ccj_ctx *c) {
-    if (!c->comm) {
-        HIPCHK(c, hipEventSynchronize(c->ev_end));
+    if (!c->xch.comm) {
+        HIPCHK(c, hipEventSynchronize(c->fs.ev_end));
         return CCJ_OK;
     }
     static const double limit_s = [] {
@@ -1616,20 +1682,20 @@ static int wait_fill_end(ccj_ctx *c) {
     }();
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
-        const hipError_t q = hipEventQuery(c->ev_end);
+        const hipError_t q = hipEventQuery(c->fs.ev_end);
         if (q == hipSuccess) return CCJ_OK;
         if (q != hipErrorNotReady) return set_err(c, CCJ_E_HIP, "fill: %s", hipGetErrorString(q));
         ncclResult_t ae = ncclSuccess, ae2 = ncclSuccess;
-        ncclResult_t qr = ncclCommGetAsyncError(c->comm, &ae);
-        if (qr == ncclSuccess && ae == ncclSuccess && c->comm_b) {  // the bulk communicator too
-            qr = ncclCommGetAsyncError(c->comm_b, &ae2);
+        ncclResult_t qr = ncclCommGetAsyncError(c->xch.comm, &ae);
+        if (qr == ncclSuccess && ae == ncclSuccess && c->xch.comm_b) {  // the bulk communicator too
+            qr = ncclCommGetAsyncError(c->xch.comm_b, &ae2);
             ae = ae2;
         }
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (qr != ncclSuccess || ae != ncclSuccess || el > limit_s) {
-            if (c->comm_b) ncclCommAbort(c->comm_b);
-            ncclCommAbort(c->comm);
-            c->comm = c->comm_b = nullptr;
+            if (c->xch.comm_b) ncclCommAbort(c->xch.comm_b);
+            ncclCommAbort(c->xch.comm);
+            c->xch.comm = c->xch.comm_b = nullptr;
             if (qr != ncclSuccess || ae != ncclSuccess)
                 return set_err(c, CCJ_E_COMM, "band-sharded exchange failed: %s",
                                ncclGetErrorString(qr != ncclSuccess ? qr : ae));
@@ -1674,9 +1740,9 @@ static int fill_finish(ccj_ctx *c) {
     if (herr & 1) return set_err(c, CCJ_E_PARAMS, "e_intP table value outside int16 range (flags %d)", herr);
     if (herr & ~ERR_RANGE_MASK) return set_err(c, CCJ_E_HIP, "device bounds check failed (flags %d)", herr);
     int rflags = (herr & ERR_RANGE_MASK) >> ERR_RANGE_SHIFT;
-    if (c->lgroup) {
+    if (c->xch.lgroup) {
         // in-process group: a rank saw the sites of its own blocks; every rank reports the union
-        ccj_group *g = c->lgroup;
+        ccj_group *g = c->xch.lgroup;
         const int slot = (int)(c->range_gen++ & 1);
         {
             std::lock_guard<std::mutex> lk(g->mu);
@@ -1694,9 +1760,9 @@ static int fill_finish(ccj_ctx *c) {
         }
     }
     float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_end));
+    HIPCHK(c, hipEventElapsedTime(&ms, c->fs.ev_start, c->fs.ev_end));
     c->fill_ms = ms;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_start, c->ev_pre));
+    HIPCHK(c, hipEventElapsedTime(&ms, c->fs.ev_start, c->fs.ev_pre));
     c->pre_ms = ms;
     double lsum = 0, dsum = 0, isum = 0;
     c->lev_ms_v.assign(n, 0.0);
@@ -1710,7 +1776,7 @@ static int fill_finish(ccj_ctx *c) {
         // level s = from the end of level s-1 (ev_pre for s = 0) to its lev_done on st: the waits for
         // k_iloop(s) / k_diag2d(s-1), the plain launch and the leaders
         for (int s = 0; s < c->nlev && s < n; ++s) {
-            HIPCHK(c, hipEventElapsedTime(&ms, s == 0 ? c->ev_pre : c->lev_done[s - 1], c->lev_done[s]));
+            HIPCHK(c, hipEventElapsedTime(&ms, s == 0 ? c->fs.ev_pre : c->fs.lev_done[s - 1], c->fs.lev_done[s]));
             lsum += ms;
             c->lev_ms_v[s] = ms;
         }
@@ -1733,7 +1799,7 @@ static int fill_finish(ccj_ctx *c) {
                 psum += ms;
                 c->pp_ms_v[s] = ms;
             }
-            if (c->world > 1 && !c->simulate) {
+            if (c->exchanges()) {
                 // the edge part on the level stream: waits for span s, packs, all-gather, unpacks
                 HIPCHK(c, hipEventElapsedTime(&ms, ev[6], ev[5]));
                 c->xch_ms_v[s] = ms;
@@ -2321,14 +2387,14 @@ extern "C" int ccj_comm_init(ccj_ctx *c, const char *id_in) {
     HIPCHK(c, hipSetDevice(c->device));
     ncclUniqueId id;
     memcpy(&id, id_in, sizeof id);
-    if (c->comm_b) ncclCommDestroy(c->comm_b);
-    if (c->comm) ncclCommDestroy(c->comm);
-    c->comm = c->comm_b = nullptr;
-    const ncclResult_t r = ncclCommInitRank(&c->comm, c->world, id, c->rank);
+    if (c->xch.comm_b) ncclCommDestroy(c->xch.comm_b);
+    if (c->xch.comm) ncclCommDestroy(c->xch.comm);
+    c->xch.comm = c->xch.comm_b = nullptr;
+    const ncclResult_t r = ncclCommInitRank(&c->xch.comm, c->world, id, c->rank);
     if (r != ncclSuccess) return set_err(c, CCJ_E_HIP, "ncclCommInitRank: %s", ncclGetErrorString(r));
     // the bulk all-gathers run on their own stream: their own communicator (same ranks, same order), so
     // the two streams' collectives never queue behind each other inside one communicator
-    const ncclResult_t r2 = ncclCommSplit(c->comm, 0, c->rank, &c->comm_b, nullptr);
+    const ncclResult_t r2 = ncclCommSplit(c->xch.comm, 0, c->rank, &c->xch.comm_b, nullptr);
     if (r2 != ncclSuccess) return set_err(c, CCJ_E_HIP, "ncclCommSplit: %s", ncclGetErrorString(r2));
     return CCJ_OK;
 }
@@ -2349,7 +2415,7 @@ extern "C" int ccj_comm_init_local(ccj_ctx *c, ccj_group *g) {
     if (g->members[c->rank] && g->members[c->rank] != c)
         return set_err(c, CCJ_E_STATE, "ccj_comm_init_local: rank %d of the group is already taken", c->rank);
     g->members[c->rank] = c;
-    c->lgroup = g;
+    c->xch.lgroup = g;
     return CCJ_OK;
 }
 
@@ -2360,8 +2426,8 @@ extern "C" int ccj_range_flags(const ccj_ctx *c) { return c ? c->range_flags : 0
 extern "C" void ccj_destroy(ccj_ctx *c) {
     if (!c || c->batch) return;  // a batch member is borrowed: ccj_batch_destroy frees it
     bool leak_send = false;
-    if (c->lgroup) {  // leave the in-process group: no member may copy from this context's buffers
-        ccj_group *g = c->lgroup;
+    if (c->xch.lgroup) {  // leave the in-process group: no member may copy from this context's buffers
+        ccj_group *g = c->xch.lgroup;
         std::unique_lock<std::mutex> lk(g->mu);
         if (g->members[c->rank] == c) {  // registered (a failed ccj_comm_init_local never was)
             g->members[c->rank] = nullptr;
@@ -2376,53 +2442,25 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
         }
         // the peers' asynchronous bulk copies (local_bulk_gather) from this member's send slice
         for (ccj_ctx *p : g->members)
-            if (p && p->st_x) hipStreamSynchronize(p->st_x);
-        c->lgroup = nullptr;
+            if (p && p->xch.st_x) hipStreamSynchronize(p->xch.st_x);
+        c->xch.lgroup = nullptr;
     }
     hipSetDevice(c->device);
-    if (c->st) hipStreamSynchronize(c->st);
-    if (c->st_copy) hipStreamSynchronize(c->st_copy);
-    if (c->st_p) hipStreamSynchronize(c->st_p);
-    if (c->st_il) hipStreamSynchronize(c->st_il);
-    if (c->st_d) hipStreamSynchronize(c->st_d);
-    if (c->st_x) hipStreamSynchronize(c->st_x);
-    hipFree(c->d4);
-    hipFree(c->d_ie);
-    hipFree(c->d_est);
-    hipFree(c->d_hp);
-    hipFree(c->d_pt);
-    hipFree(c->d_pair);
-    hipFree(c->d_rtype);
-    hipFree(c->d_lx);
-    hipFree(c->d_err);
-    hipFree(c->d_S);
-    hipFree(c->d_S1);
-    hipFree(c->d_prm);
-    hipFree(c->d_lv);
-    hipFree(c->d_lb);
-    hipFree(c->d_ld);
-    hipFree(c->d4x_alloc);
-    hipFree(c->d_icount);
-    hipFree(c->d_ioff);
-    hipFree(c->d_rec);
-    hipFree(c->d_rk);
-    hipFree(c->d_rl);
-    hipFree(c->d_cf);
-    hipFree(c->d_acc);
-    hipFree(c->d_wterm);
-    hipFree(c->d_lord);
-    hipFree(c->d_lord_off);
-    hipFree(c->d_wbw);
-    hipFree(c->d_tab);
-    hipFree(c->pmx_alloc);
-    hipFree(c->d_ldx);
-    hipFree(c->d_il);
-    hipFree(c->d_ilm);
-    hipFree(c->d_dummy);
-    hipFree(c->d_items);
+    Exchange &x = c->xch;
+    for (hipStream_t q : {c->st, c->st_copy, c->fs.st_p, c->fs.st_il, x.st_d, x.st_x})
+        if (q) hipStreamSynchronize(q);
+    for (void *p : {(void *)c->d4, (void *)c->d_ie, (void *)c->d_est, (void *)c->d_hp, (void *)c->d_pt, (void *)c->d_pair,
+                    (void *)c->d_rtype, (void *)c->d_lx, (void *)c->d_err, (void *)c->d_S, (void *)c->d_S1, (void *)c->d_prm,
+                    (void *)c->d_lv, (void *)c->d_lb, (void *)c->d_ld, (void *)c->d4x_alloc, (void *)c->d_icount,
+                    (void *)c->d_ioff, (void *)c->d_rec, (void *)c->d_rk, (void *)c->d_rl, (void *)c->d_cf, (void *)c->d_acc,
+                    (void *)c->d_wterm, (void *)c->d_lord, (void *)c->d_lord_off, (void *)c->d_wbw, (void *)c->d_tab,
+                    (void *)c->pmx_alloc, (void *)c->d_ldx, (void *)c->d_il, (void *)c->d_ilm, (void *)c->d_dummy,
+                    (void *)c->d_items, (void *)c->d_ilseg, (void *)c->d_ilmseg, (void *)c->d2i, (void *)c->d_pk, (void *)c->d_W,
+                    (void *)c->d_fpair, (void *)c->d_ftype, (void *)c->d_btout, (void *)c->d_vt})
+        hipFree(p);
     for (int part = 0; part < 2; ++part) {
-        if (!leak_send) hipFree(c->d_send[part]);
-        hipFree(c->d_recv[part]);
+        if (!leak_send) hipFree(x.d_send[part]);
+        hipFree(x.d_recv[part]);
     }
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_bind) hipHostFree(c->h_bind);
@@ -2435,36 +2473,17 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
     if (c->hr_ft) hipHostFree(c->hr_ft);
     if (c->hr_bo) hipHostFree(c->hr_bo);
     if (c->ev_res) hipEventDestroy(c->ev_res);
-    hipFree(c->d_ilseg);
-    hipFree(c->d_ilmseg);
-    hipFree(c->d2i);
-    hipFree(c->d_pk);
-    hipFree(c->d_W);
-    hipFree(c->d_fpair);
-    hipFree(c->d_ftype);
-    hipFree(c->d_btout);
-    hipFree(c->d_vt);
     if (c->h4) hipHostFree(c->h4);
-    for (auto e : c->lev_done) hipEventDestroy(e);
-    for (auto e : c->p_done) hipEventDestroy(e);
-    for (auto e : c->pp_done) hipEventDestroy(e);
-    for (auto e : c->bulk_done) hipEventDestroy(e);
-    if (c->ev_bpacked) hipEventDestroy(c->ev_bpacked);
-    if (c->ev_bcopied) hipEventDestroy(c->ev_bcopied);
-    if (c->st_p) hipStreamDestroy(c->st_p);
-    if (c->st_x) hipStreamDestroy(c->st_x);
-    if (c->comm_b) ncclCommDestroy(c->comm_b);
-    if (c->comm) ncclCommDestroy(c->comm);
-    if (c->st_il) hipStreamDestroy(c->st_il);
-    if (c->st_d) hipStreamDestroy(c->st_d);
-    for (auto e : c->il_done) hipEventDestroy(e);
-    for (auto e : c->dg_done) hipEventDestroy(e);
-    for (auto e : c->tev) hipEventDestroy(e);
-    if (c->ev_start) hipEventDestroy(c->ev_start);
-    if (c->ev_end) hipEventDestroy(c->ev_end);
-    if (c->ev_pre) hipEventDestroy(c->ev_pre);
-    if (c->st) hipStreamDestroy(c->st);
-    if (c->st_copy) hipStreamDestroy(c->st_copy);
+    for (auto *v : {&x.pp_done, &x.bulk_done, &c->tev})
+        for (hipEvent_t e : *v)
+            if (e) hipEventDestroy(e);
+    for (hipEvent_t e : {x.ev_bpacked, x.ev_bcopied})
+        if (e) hipEventDestroy(e);
+    if (x.comm_b) ncclCommDestroy(x.comm_b);
+    if (x.comm) ncclCommDestroy(x.comm);
+    fill_sync_destroy(c->fs);
+    for (hipStream_t q : {x.st_d, x.st_x, c->st, c->st_copy})
+        if (q) hipStreamDestroy(q);
     delete c;
 }
 
@@ -2472,9 +2491,9 @@ extern "C" void ccj_destroy(ccj_ctx *c) {
 // Lockstep batch (include/ccj.h): K capacity contexts whose fills run as ONE
 // wavefront over the steps s = 0 .. max(n_k)-1.  Every kernel of a step is launched once for all
 // bound members (ccj_engine.h k_*_many), so the per-level chain of launches and events, which is
-// what a short fold costs, is paid once per batch.  The event DAG is fill_enqueue's unsharded one
-// (il_done, lev_done, p_done, dg_done by step) on the batch's own streams.  Members never share
-// split points (created with sharing off: g_lo = g_hi = 0, no leader launch).
+// what a short fold costs, is paid once per batch.  The graph is enqueue_level_dag, on the batch's
+// own streams and events (by step), with BatchLaunch's launches.  Members never share split points
+// (created with sharing off: g_lo = g_hi = 0, no leader launch).
 // ============================================================================================
 struct ccj_batch {
     int device = 0, ncap = 0, K = 0;
@@ -2483,9 +2502,9 @@ struct ccj_batch {
     int split_target = 0;
     std::vector<ccj_ctx *> m;
     std::vector<int> n;       // bound lengths
-    hipStream_t st = nullptr, st_p = nullptr, st_il = nullptr, st_d = nullptr;
-    std::vector<hipEvent_t> il_done, dg_done, lev_done, p_done;
-    hipEvent_t ev_start = nullptr, ev_pre = nullptr, ev_end = nullptr, ev_res = nullptr, ev_args = nullptr;
+    hipStream_t st = nullptr;
+    FillSync fs;
+    hipEvent_t ev_res = nullptr, ev_args = nullptr;
     // per member: tables, result pointers; per (step, member): launch arguments; device + pinned staging
     DevTables *d_tabs = nullptr, *h_tabs = nullptr;
     BatchRes *d_res = nullptr, *h_res = nullptr;
@@ -2518,10 +2537,30 @@ static int batch_err(ccj_batch *b, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return batch_err((b), CCJ_E_HIP, "%s: %s", #x, hipGetErrorString(e_)); \
     } while (0)
 
+// A batch's launches for enqueue_level_dag: one k_*_many per family over the cnt bound members, with
+// the step's rows of launch arguments (device, and the pinned staging they were uploaded from).
+struct BatchLaunch {
+    const ccj_batch *b;
+    int cnt, nb;
+    const LevelArgs *row(int s) const { return b->d_args + (size_t)s * b->K; }
+    const LevelArgs *hrow(int s) const { return b->h_args + (size_t)s * b->K; }
+    hipError_t pre(hipStream_t q) const { return (hipError_t)ccjk_pre_many(b->d_tabs, cnt, nb, q); }
+    hipError_t iloop(int s, hipStream_t q) const { return (hipError_t)ccjk_iloop_many(b->d_tabs, row(s), hrow(s), cnt, s, q); }
+    hipError_t diag(int sg, hipStream_t q) const { return (hipError_t)ccjk_diag2d_many(b->d_tabs, row(sg), hrow(sg), cnt, sg, q); }
+    // behind the last span: every member's closed-form range check (site CF)
+    hipError_t behind_span(int sg, hipStream_t q) const {
+        return sg == nb - 1 ? (hipError_t)ccjk_cf_low_many(b->d_tabs, cnt, nb, q) : hipSuccess;
+    }
+    hipError_t level(int s, hipStream_t q) const {
+        return (hipError_t)ccjk_level4d_many(b->d_tabs, row(s), b->n.data(), cnt, s, b->split_target, q);
+    }
+    hipError_t ppush(int s, hipStream_t q) const { return (hipError_t)ccjk_ppush_many(b->d_tabs, row(s), hrow(s), cnt, s, q); }
+};
+
 extern "C" void ccj_batch_destroy(ccj_batch *b) {
     if (!b) return;
     hipSetDevice(b->device);
-    for (hipStream_t q : {b->st, b->st_p, b->st_il, b->st_d})
+    for (hipStream_t q : {b->st, b->fs.st_p, b->fs.st_il})
         if (q) hipStreamSynchronize(q);
     for (ccj_ctx *c : b->m) {
         if (!c) continue;
@@ -2546,12 +2585,10 @@ extern "C" void ccj_batch_destroy(ccj_batch *b) {
     for (void *p : {(void *)b->h_tabs, (void *)b->h_res, (void *)b->h_args, (void *)b->h_W, (void *)b->h_fp, (void *)b->h_ft,
                     (void *)b->h_bo, (void *)b->h_err})
         if (p) hipHostFree(p);
-    for (auto *v : {&b->il_done, &b->dg_done, &b->lev_done, &b->p_done})
-        for (hipEvent_t e : *v) hipEventDestroy(e);
-    for (hipEvent_t e : {b->ev_start, b->ev_pre, b->ev_end, b->ev_res, b->ev_args})
+    for (hipEvent_t e : {b->ev_res, b->ev_args})
         if (e) hipEventDestroy(e);
-    for (hipStream_t q : {b->st, b->st_p, b->st_il, b->st_d})
-        if (q) hipStreamDestroy(q);
+    fill_sync_destroy(b->fs);
+    if (b->st) hipStreamDestroy(b->st);
     delete b;
 }
 
@@ -2580,16 +2617,8 @@ static int batch_create_impl(const ccj_problem *p, const ccj_options *o, int nma
         if (b->m[k]->full4) return batch_err(b, CCJ_E_ARG, "a lockstep batch needs lean members (CCJ_D4_FULL is set)");
     }
     b->split_target = b->m[0]->split_target;
-    for (hipStream_t *q : {&b->st, &b->st_p, &b->st_il, &b->st_d}) BHIP(b, hipStreamCreateWithFlags(q, hipStreamNonBlocking));
-    const unsigned sync_fl = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
-    const size_t nev = (size_t)nmax + 1;
-    for (auto *v : {&b->il_done, &b->dg_done, &b->lev_done, &b->p_done}) {
-        v->assign(nev, nullptr);
-        for (auto &e : *v) BHIP(b, hipEventCreateWithFlags(&e, sync_fl));
-    }
-    BHIP(b, hipEventCreate(&b->ev_start));
-    BHIP(b, hipEventCreate(&b->ev_pre));
-    BHIP(b, hipEventCreate(&b->ev_end));
+    BHIP(b, hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+    BHIP(b, fill_sync_create(b->fs, (size_t)nmax + 1, false));
     BHIP(b, hipEventCreateWithFlags(&b->ev_res, hipEventDisableTiming));
     BHIP(b, hipEventCreateWithFlags(&b->ev_args, hipEventDisableTiming));
     const size_t K = (size_t)members, st = b->stride(), nargs = (size_t)nmax * K;
@@ -2710,55 +2739,16 @@ extern "C" int ccj_batch_fold_async(ccj_batch *b) {
     if (b->count < 1) return batch_err(b, CCJ_E_STATE, "ccj_batch_fold_async: no binding (ccj_batch_bind first)");
     BHIP(b, hipSetDevice(b->device));
     const int cnt = b->count, nb = b->nb, nlev = nb > 2 ? nb - 2 : 0;
-    const size_t K = (size_t)b->K;
     hipStream_t st = b->st;
     for (int k = 0; k < cnt; ++k) {
         ccj_ctx *c = b->m[k];
         c->filled = c->mirrored = c->mirrored2d = c->res_ready = false;
     }
-    auto row = [&](int s) { return b->d_args + (size_t)s * K; };
-    auto hrow = [&](int s) { return b->h_args + (size_t)s * K; };
     BHIP(b, hipMemsetAsync(b->d_err, 0, cnt * sizeof(int), st));
-    BHIP(b, hipEventRecord(b->ev_start, st));
-    BHIP(b, (hipError_t)ccjk_pre_many(b->d_tabs, cnt, nb, st));
-    BHIP(b, hipEventRecord(b->ev_pre, st));
-    BHIP(b, hipStreamWaitEvent(b->st_il, b->ev_pre, 0));
-    BHIP(b, hipStreamWaitEvent(b->st_p, b->ev_pre, 0));
-    // k_diag2d(sg) behind k_iloop(sg+1) on st_il (fill_enqueue's join_diag), after P(sg)
-    auto enqueue_diag = [&](int sg) -> int {
-        if (sg >= 3) BHIP(b, hipStreamWaitEvent(b->st_il, b->p_done[sg], 0));
-        BHIP(b, (hipError_t)ccjk_diag2d_many(b->d_tabs, row(sg), hrow(sg), cnt, sg, b->st_il));
-        BHIP(b, hipEventRecord(b->dg_done[sg], b->st_il));
-        return CCJ_OK;
-    };
-    for (int s = 0; s < nb; ++s) {
-        if (s >= nlev) {
-            if (s == nlev && s >= 1) {
-                if (const int rc = enqueue_diag(s - 1)) return rc;
-            }
-            if (const int rc = enqueue_diag(s)) return rc;
-            continue;
-        }
-        if (s >= 3) BHIP(b, hipStreamWaitEvent(b->st_il, b->lev_done[s - 3], 0));
-        BHIP(b, (hipError_t)ccjk_iloop_many(b->d_tabs, row(s), hrow(s), cnt, s, b->st_il));
-        if (s >= 1) {
-            if (const int rc = enqueue_diag(s - 1)) return rc;
-        }
-        BHIP(b, hipEventRecord(b->il_done[s], b->st_il));
-        BHIP(b, hipStreamWaitEvent(st, b->il_done[s], 0));
-        BHIP(b, (hipError_t)ccjk_level4d_many(b->d_tabs, row(s), b->n.data(), cnt, s, b->split_target, st));
-        BHIP(b, hipEventRecord(b->lev_done[s], st));
-        if (s + 3 < nb) {  // the P terms level s completes: P(s+3)
-            BHIP(b, hipStreamWaitEvent(b->st_p, b->lev_done[s], 0));
-            BHIP(b, (hipError_t)ccjk_ppush_many(b->d_tabs, row(s), hrow(s), cnt, s, b->st_p));
-            BHIP(b, hipEventRecord(b->p_done[s + 3], b->st_p));
-        }
-    }
-    // behind the last span on its stream: every member's closed-form range check (site CF)
-    BHIP(b, (hipError_t)ccjk_cf_low_many(b->d_tabs, cnt, nb, b->st_il));
-    BHIP(b, hipEventRecord(b->dg_done[nb - 1], b->st_il));
-    BHIP(b, hipStreamWaitEvent(st, b->dg_done[nb - 1], 0));
-    BHIP(b, hipEventRecord(b->ev_end, st));
+    BHIP(b, hipEventRecord(b->fs.ev_start, st));
+    BHIP(b, enqueue_level_dag(b->fs, st, nb, nlev, BatchLaunch{b, cnt, nb}));
+    BHIP(b, hipStreamWaitEvent(st, b->fs.dg_done[nb - 1], 0));
+    BHIP(b, hipEventRecord(b->fs.ev_end, st));
     // W and the traceback, one workgroup per member, then one copy per result array
     int capmax = 0;
     for (int k = 0; k < cnt; ++k) capmax = std::max(capmax, bt_stack_cap(b->n[k]));
@@ -2782,7 +2772,7 @@ extern "C" int ccj_batch_wait(ccj_batch *b) {
     BHIP(b, hipSetDevice(b->device));
     BHIP(b, hipEventSynchronize(b->ev_res));
     float ms = 0;
-    BHIP(b, hipEventElapsedTime(&ms, b->ev_start, b->ev_end));
+    BHIP(b, hipEventElapsedTime(&ms, b->fs.ev_start, b->fs.ev_end));
     b->fill_ms = ms;
     int rc = CCJ_OK;
     for (int k = 0; k < b->count; ++k) {
