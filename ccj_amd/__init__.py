@@ -21,7 +21,7 @@ __all__ = [
     "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
-    "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
+    "pf_many", "pf_setup_host_hashes", "PF_SETUP_TABLES", "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +43,7 @@ PF_MAT4 = ["PK", "PL", "PR", "PM", "PO", "PfromL", "PfromR", "PfromM", "PfromO",
            "PMmloop00", "PMmloop01", "PMmloop10", "POmloop00", "POmloop01", "POmloop10"]
 PF_MAT2 = ["V", "VM", "WM", "WMv", "WMp", "WBP", "WPP", "P"]
 CCJ_E_PF_SAMPLE = 8  # include/ccj_pf.h
+CCJ_E_PF_RANGE = 10
 
 CCJ_OK, CCJ_E_ARG, CCJ_E_OOM, CCJ_E_HIP, CCJ_E_PARAMS, CCJ_E_BACKTRACK, CCJ_E_STATE, CCJ_E_INTER_EXIT = range(8)
 CCJ_E_COMM = 9  # include/ccj.h: band-sharded exchange failed or timed out
@@ -238,6 +239,25 @@ def lib() -> ctypes.CDLL:
     L.ccj_pf_create.restype = ip
     L.ccj_pf_destroy.argtypes = [vp]
     L.ccj_pf_destroy.restype = None
+    # (a CCJ_LIB_VARIANT built from an older tree, as the A side of tools/pf_contexts_ab.py, has no
+    # capacity entry points: calling one there is an AttributeError, not a fallback)
+    if hasattr(L, "ccj_pf_create_cap"):
+        L.ccj_pf_create_cap.argtypes = [ctypes.POINTER(_Problem), cp, ip, ip, ctypes.POINTER(vp)]
+        L.ccj_pf_create_cap.restype = ip
+        L.ccj_pf_rebind.argtypes = [vp, cp]
+        L.ccj_pf_rebind.restype = ip
+        L.ccj_pf_reset.argtypes = [vp, cp]
+        L.ccj_pf_reset.restype = ip
+        L.ccj_pf_capacity.argtypes = [vp]
+        L.ccj_pf_capacity.restype = ip
+        L.ccj_pf_n.argtypes = [vp]
+        L.ccj_pf_n.restype = ip
+        L.ccj_pf_keytab_info.argtypes = [vp, dp, ctypes.POINTER(ctypes.c_ulonglong)]
+        L.ccj_pf_keytab_info.restype = ip
+        L.ccj_pf_setup_hashes.argtypes = [vp, u64p, ip]
+        L.ccj_pf_setup_hashes.restype = ip
+        L.ccj_pf_setup_host_hashes.argtypes = [ctypes.POINTER(_Problem), cp, u64p, u64p]
+        L.ccj_pf_setup_host_hashes.restype = ip
     L.ccj_pf_fill.argtypes = [vp, dp]
     L.ccj_pf_fill.restype = ip
     L.ccj_pf_W.argtypes = [vp, dp]
@@ -916,6 +936,67 @@ class SampleExit(CCJError):
         self.structures = structures
 
 
+PF_SETUP_TABLES = ["pt", "est", "hp", "items", "ieO", "ieI", "mO", "mI"]  # ccj_pf_setup_hashes
+
+
+def _pf_problem(seq, dangle, params, noGU, pen):
+    """A ccj_problem for the partition function and the buffers it points into (keep them alive)."""
+    blob = params if isinstance(params, (bytes, bytearray)) else load_params(params)
+    blob_buf = ctypes.create_string_buffer(bytes(blob), len(blob))
+    seq_buf = ctypes.create_string_buffer(seq.encode()) if seq is not None else None
+    pen_s = None
+    if pen is not None:
+        if len(pen) != 14:
+            raise CCJError(CCJ_E_ARG, "pen needs the 14 values of ccj_pk_penalties")
+        pen_s = _Penalties(*[int(v) for v in pen[:12]], float(pen[12]), float(pen[13]))
+    prob = _Problem(ctypes.cast(seq_buf, ctypes.c_char_p) if seq_buf is not None else None, dangle, 1 if noGU else 0,
+                    ctypes.cast(blob_buf, ctypes.c_void_p),
+                    ctypes.cast(ctypes.pointer(pen_s), ctypes.c_void_p) if pen_s is not None else None)
+    return prob, (blob_buf, seq_buf, pen_s)
+
+
+def pf_setup_host_hashes(seq: str, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False,
+                         pen=None) -> tuple:
+    """No GPU: FNV hashes of a problem's setup tables (est, ieO, ieI, mO, mI; the windows over the
+    intervals whose pair can pair) built two ways — one pow per entry, and through the key tables
+    and the gather functions the setup kernels share (ccj_pf_setup_host_hashes).  (direct, keyed)."""
+    prob, keep = _pf_problem(seq, dangle, params, noGU, pen)
+    names = ["est", "ieO", "ieI", "mO", "mI"]
+    a, b = (ctypes.c_uint64 * 5)(), (ctypes.c_uint64 * 5)()
+    rc = lib().ccj_pf_setup_host_hashes(ctypes.byref(prob), load_pfraw(params), a, b)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "ccj_pf_setup_host_hashes")
+    return ({k: "%016x" % v for k, v in zip(names, a)}, {k: "%016x" % v for k, v in zip(names, b)})
+
+
+def pf_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False, device: int = 0,
+            capacity: Optional[int] = None) -> list:
+    """The partition function of every sequence through one capacity context (capacity: the longest
+    sequence by default), rebind + fill each.  Returns one record per sequence, in input order:
+    (seq, energy, W(n)).  A fold that fails (CCJ_E_PF_RANGE: the exactness guard) is recorded as
+    (seq, None, CCJError) and does not disturb the others."""
+    seqs = list(seqs)
+    if not seqs:
+        return []
+    cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
+    out: list = []
+    pf = W_final_pf(seqs[0], dangle=dangle, params=params, noGU=noGU, device=device, capacity=cap)
+    try:
+        for x, s in enumerate(seqs):
+            if x:
+                pf.rebind(s)
+            try:
+                e = pf.ccj_pf()
+                out.append((s, e, pf.W()[-1]))
+            except CCJError as ex:
+                if ex.code != CCJ_E_PF_RANGE:
+                    raise
+                out.append((s, None, ex))
+    finally:
+        pf.close()
+    return out
+
+
 class W_final_pf:
     """Mirror of the reference class W_final_pf (src/part_func.hh:28-194, part_func.cc).
 
@@ -930,7 +1011,10 @@ class W_final_pf:
 
     def __init__(self, seq: str, MFE_structure: str = "", MFE_energy: float = 0.0, dangle: int = 2,
                  num_samples: int = 0, PSplot: bool = False, params: str | bytes = "DirksPierce09",
-                 noGU: bool = False, device: int = 0):
+                 noGU: bool = False, device: int = 0, pen=None, capacity: Optional[int] = None):
+        """capacity=N: a context that folds any sequence of length 1..N (include/ccj_pf.h
+        ccj_pf_create_cap); reset(seq) / rebind(seq) then bind the next sequence without allocating.
+        pen: the 14 pseudoknot penalties, as for W_final."""
         self.seq = seq
         self.n = len(seq)
         self.MFE_structure = MFE_structure
@@ -939,15 +1023,15 @@ class W_final_pf:
         self.PSplot = PSplot
         self.structure = "." * self.n
         self.structures: dict = {}
-        self._blob = params if isinstance(params, (bytes, bytearray)) else load_params(params)
-        self._blob_buf = ctypes.create_string_buffer(bytes(self._blob), len(self._blob))
-        self._seq_buf = ctypes.create_string_buffer(seq.encode())
+        self._h = None
         L = lib()
-        prob = _Problem(ctypes.cast(self._seq_buf, ctypes.c_char_p), dangle, 1 if noGU else 0,
-                        ctypes.cast(self._blob_buf, ctypes.c_void_p), None)
+        prob, self._keep = _pf_problem(seq, dangle, params, noGU, pen)
         h = ctypes.c_void_p()
         self._raw = load_pfraw(params)
-        rc = L.ccj_pf_create(ctypes.byref(prob), self._raw, device, ctypes.byref(h))
+        if capacity is None:
+            rc = L.ccj_pf_create(ctypes.byref(prob), self._raw, device, ctypes.byref(h))
+        else:
+            rc = L.ccj_pf_create_cap(ctypes.byref(prob), self._raw, device, int(capacity), ctypes.byref(h))
         if rc != CCJ_OK:
             raise CCJError(rc, "ccj_pf_create failed (see stderr)")
         self._h = h
@@ -956,6 +1040,43 @@ class W_final_pf:
     def _check(self, rc: int):
         if rc != CCJ_OK:
             raise CCJError(rc, lib().ccj_pf_last_message(self._h).decode())
+
+    def _bound(self, seq: str) -> None:
+        self.seq = seq
+        self.n = len(seq)
+        self.structure = "." * self.n
+        self.energy = None
+
+    def reset(self, seq: str) -> None:
+        """Bind another sequence of the same length (ccj_pf_reset): the per-sequence tables are
+        rebuilt on the GPU, nothing is allocated; the context holds no fill until ccj_pf()."""
+        if len(seq) != self.n:
+            raise CCJError(CCJ_E_ARG, f"reset: length {len(seq)} differs from n={self.n}")
+        self._check(lib().ccj_pf_reset(self._h, seq.encode()))
+        self._bound(seq)
+
+    def rebind(self, seq: str) -> None:
+        """Bind another sequence of any length up to the capacity (ccj_pf_rebind); with the bound
+        length it is reset()."""
+        self._check(lib().ccj_pf_rebind(self._h, seq.encode()))
+        self._bound(seq)
+
+    @property
+    def capacity(self) -> int:
+        """The longest sequence this context can be bound to (ccj_pf_capacity)."""
+        return lib().ccj_pf_capacity(self._h)
+
+    def keytab_info(self) -> tuple:
+        """(host ms of this context's one-time key-table build, its device bytes)."""
+        ms, b = ctypes.c_double(), ctypes.c_ulonglong()
+        self._check(lib().ccj_pf_keytab_info(self._h, ctypes.byref(ms), ctypes.byref(b)))
+        return ms.value, b.value
+
+    def setup_hashes(self) -> dict:
+        """FNV hashes of the bound sequence's setup tables on the device (ccj_pf_setup_hashes)."""
+        out = (ctypes.c_uint64 * len(PF_SETUP_TABLES))()
+        self._check(lib().ccj_pf_setup_hashes(self._h, out, len(PF_SETUP_TABLES)))
+        return {k: "%016x" % v for k, v in zip(PF_SETUP_TABLES, out)}
 
     def ccj_pf(self) -> float:
         e = ctypes.c_double()

@@ -6,6 +6,9 @@
 // (HairpinE :214-220 with the special-hairpin strstr cases, get_e_stP / get_e_intP :877-891, which
 // call pow()), drives the level-synchronous fill of ccj_pf.hip, then runs W (:163-172) and the
 // stochastic traceback (stoch_backtrack.cc:36-326) on the host over the 2-D matrices.
+// A context serves many sequences (ccj_pf_create_cap / ccj_pf_rebind / ccj_pf_reset): the pow()
+// values are tabulated once per context by their arguments (ccj_pf_setup.h) and the per-sequence
+// tables are gathered from them by kernels; CCJ_PF_HOST_SETUP=1 keeps the direct host builder.
 //
 // Everything here is evaluated as written, without floating-point contraction, with the host
 // libm — the same exp/log/pow/sin the reference links — so the device only ever multiplies and
@@ -28,6 +31,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
 #include <new>
 #include <string>
@@ -39,6 +43,7 @@
 #include "ccj_pf_energy.h"
 #include "ccj_pf_engine.h"
 #include "ccj_items.h"
+#include "ccj_pf_setup.h"
 
 using namespace ccj;
 
@@ -161,6 +166,8 @@ constexpr int kNExp = 22;
 
 struct ccj_pf_ctx {
     int n = 0, rs = 0, dangles = 2, device = 0;
+    int cap = 0;     // capacity N: every buffer holds any length 1..N (ccj_pf_create_cap)
+    int noGU = 0;
     std::string seq;
     ccj_energy_params prm{};
     ccj_pk_penalties pen{};
@@ -168,9 +175,22 @@ struct ccj_pf_ctx {
     int rtype[8]{};
     std::vector<short> S, S1;
     PfExp E{};
-    std::vector<double> mlb, cpp, pup, hp;
+    std::vector<double> mlb, cpp, pup;  // powers up to the capacity
     std::vector<PfLvl> lv;
     long long cells = 0;  // cells of one 4-D matrix
+    long long offx = 0, offm = 0;  // bound extents of d_cx / d_pmx (ints)
+    // key tables (ccj_pf_setup.h): built once per context, gathered by every sequence setup
+    double *d_ietab = nullptr, *d_esttab = nullptr;
+    double esttab[64]{};
+    double keytab_ms = 0;
+    long long *d_icount = nullptr, *d_ioff = nullptr;  // k_pf_items: items per (level, split), first item
+    long long items_cap = 0;                           // d_items holds this many
+    // pinned staging of the asynchronous uploads / the item counts; reused only after the wait of
+    // the setup that filled it (setup_seq)
+    short *h_S = nullptr;       // S then S1, cap+2 each
+    double *h_hp = nullptr;     // [w][p] HairpinE of the bound sequence
+    PfLvl *h_lv = nullptr;
+    long long *h_icount = nullptr, *h_ioff = nullptr;
     // device
     PfExp *d_E = nullptr;
     short *d_S = nullptr, *d_S1 = nullptr;
@@ -219,6 +239,23 @@ struct ccj_pf_ctx {
 
 // The allocations of ccj_pf_create for a sequence of length n, in bytes: device (every hipMalloc
 // of create_impl; the work items, sequence-dependent, by their count when every pair can pair) and host (the two get_e_intP window tables, built before they are uploaded).
+// The items' upper bound of ccj_pf_footprint alone.  It grows with n (a longer sequence adds rows
+// to every level and levels on top), so the bound at the capacity covers every shorter length.
+static unsigned long long pf_items_bound(int n) {
+    unsigned long long rows = 0;
+    for (int t = 0; t <= n - 3; ++t) {
+        const int mi = n - t - 2;
+        for (int i = 1; i <= mi; ++i) rows += (unsigned long long)std::max(0, t - 5) * ((mi - i) / 64 + 1);
+        for (int q = 0; q < mi; ++q) rows += (unsigned long long)std::max(0, t - 5) * (q / 64 + 1);
+        for (int h = 0; h <= mi - 1; ++h)
+            for (int j = 1; j + h + 2 <= n; ++j) {
+                const int k = j + h + 2, alo = std::max(2, t - (n - k)), ahi = std::min(t - 2, j - 1);
+                if (alo <= ahi) rows += (unsigned long long)((ahi - alo) / 64 + 1);
+            }
+    }
+    return rows;
+}
+
 extern "C" void ccj_pf_footprint(int n, unsigned long long *device_bytes, unsigned long long *host_bytes) {
     if (n < 1) n = 1;
     const unsigned long long rs = (unsigned long long)n + 2, plane = (unsigned long long)(n + 1) * rs;
@@ -246,6 +283,7 @@ extern "C" void ccj_pf_footprint(int n, unsigned long long *device_bytes, unsign
     dev += (unsigned long long)CCJ_PF_NMAT2 * plane * sizeof(double) + 2 * plane * sizeof(long long);  // 2-D, Pacc, Pabs
     dev += 3 * plane * sizeof(double) + plane + 2ull * plane * PF_IEW * sizeof(uint32_t);             // hp, est, cp; pt; mO, mI
     dev += rows * sizeof(uint32_t) + sizeof(PfExp) + (1u << 20);                                      // items; small tables
+    dev += (unsigned long long)PF_KEYS * sizeof(double);                                              // interior-loop key table
     if (device_bytes) *device_bytes = dev;
     if (host_bytes) *host_bytes = ie;
 }
@@ -331,9 +369,13 @@ void run_threads(int total, int nthr, const std::function<void(int, int)> &f) {
 void free_dev(ccj_pf_ctx *c) {
     void *ptrs[] = {c->d_E, c->d_S, c->d_S1, c->d_pt, c->d_pair, c->d_rtype, c->d_hp, c->d_est, c->d_ieO, c->d_ieI,
                     c->d_mlb, c->d_cpp, c->d_pup, c->d_2d, c->d_Pacc, c->d_Pabs, c->d_d4, c->d_cx, c->d_pmx,
-                    c->d_prec, c->d_R, c->d_items, c->d_mO, c->d_mI, c->d_ld};
+                    c->d_prec, c->d_R, c->d_items, c->d_mO, c->d_mI, c->d_ld, c->d_ietab, c->d_esttab, c->d_icount,
+                    c->d_ioff};
     for (void *p : ptrs)
         if (p) hipFree(p);
+    void *pinned[] = {c->h_S, c->h_hp, c->h_lv, c->h_icount, c->h_ioff};
+    for (void *p : pinned)
+        if (p) hipHostFree(p);
     if (c->e0) hipEventDestroy(c->e0);
     if (c->e1) hipEventDestroy(c->e1);
     for (hipEvent_t e : c->tev) hipEventDestroy(e);
@@ -451,55 +493,24 @@ PfWork pf_work_model(const ccj_pf_ctx &c) {
     return w;
 }
 
-int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_pf_ctx *c) {
-    if (!prob || !prob->seq || !prob->params) return pf_err(c, CCJ_E_ARG, "null problem");
+// ---------------------------------------------------------------------------------------------
+// Context set-up in three parts: the model (parameters, penalties, key tables) and
+// the allocation for a capacity, once per context; binding a length; the per-sequence tables.
+// ---------------------------------------------------------------------------------------------
+
+// The model of a problem: everything of a context that does not depend on the sequence.  No GPU.
+int init_model(const ccj_problem *prob, const ccj_pf_raw *raw, ccj_pf_ctx *c) {
+    if (!prob || !prob->params) return pf_err(c, CCJ_E_ARG, "null problem");
     if (prob->params->magic != CCJ_PARAMS_MAGIC || prob->params->size_bytes != sizeof(ccj_energy_params))
         return pf_err(c, CCJ_E_ARG, "bad parameter blob");
-    c->seq = prob->seq;
-    c->n = (int)c->seq.size();
-    const int n = c->n;
-    if (n < 1) return pf_err(c, CCJ_E_ARG, "empty sequence");
-    if (n > 1023) return pf_err(c, CCJ_E_ARG, "sequence longer than 1023");
-    for (char ch : c->seq)
-        if (!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'U' || ch == 'T'))
-            return pf_err(c, CCJ_E_ARG, "sequence must be A/C/G/U/T");
+    if (raw && (raw->magic != CCJ_PF_RAW_MAGIC || raw->size_bytes != sizeof(ccj_pf_raw)))
+        return pf_err(c, CCJ_E_ARG, "bad ccj_pf_raw table");
     c->dangles = prob->dangles;
-    c->device = device;
+    c->noGU = prob->noGU ? 1 : 0;
     c->prm = *prob->params;
     const ccj_pk_penalties defp = CCJ_PK_PENALTIES_DEFAULT;
     c->pen = prob->pen ? *prob->pen : defp;
-    c->rs = n + 2;
-    const int rs = c->rs;
-    {
-        // Size check before any table is built (ccj_pf_footprint: the allocations below, summed).
-        // Past what the host or the GPU can hold, fail with CCJ_E_OOM up front instead of after
-        // seconds of table building.  CCJ_PF_DEVMEM_LIMIT (bytes) stands in for the device's free
-        // memory (tests pin the accept/reject boundary with it).
-        unsigned long long dev_b = 0, host_b = 0;
-        ccj_pf_footprint(n, &dev_b, &host_b);
-        size_t dfree = 0, dtotal = 0;
-        char msg[200];
-        const char *lim = getenv("CCJ_PF_DEVMEM_LIMIT");
-        if (lim && *lim) dfree = (size_t)strtoull(lim, nullptr, 10);
-        else if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&dfree, &dtotal) != hipSuccess) dfree = SIZE_MAX;
-        if ((double)dev_b > (double)dfree) {
-            snprintf(msg, sizeof msg, "n=%d needs ~%.1f GB of device memory, %.1f GB free", n, dev_b / 1e9, dfree / 1e9);
-            return pf_err(c, CCJ_E_OOM, msg);
-        }
-        // MemAvailable counts reclaimable page cache (sysconf(_SC_AVPHYS_PAGES) does not)
-        unsigned long long avail_kb = 0;
-        if (FILE *f = fopen("/proc/meminfo", "r")) {
-            char line[256];
-            while (fgets(line, sizeof line, f))
-                if (sscanf(line, "MemAvailable: %llu kB", &avail_kb) == 1) break;
-            fclose(f);
-        }
-        if (avail_kb > 0 && (double)host_b > (double)avail_kb * 1024.0) {
-            snprintf(msg, sizeof msg, "n=%d needs ~%.1f GB of host memory for the interior-loop tables", n, host_b / 1e9);
-            return pf_err(c, CCJ_E_OOM, msg);
-        }
-    }
-    // make_pair_matrix / encode_sequence (pair_mat.h:81-183)
+    // make_pair_matrix (pair_mat.h:81-183)
     const int base_rtype[8] = {0, 2, 1, 4, 3, 6, 5, 7};
     memcpy(c->rtype, base_rtype, sizeof base_rtype);
     for (int x = 0; x < 8; ++x)
@@ -507,6 +518,30 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
     if (prob->noGU) c->pair[3][4] = c->pair[4][3] = 0;
     for (int x = 0; x < 8; ++x)
         for (int y = 0; y < 8; ++y) c->rtype[c->pair[x][y]] = c->pair[y][x];
+    build_exp(c->prm, raw, c->pen, c->E);
+    return CCJ_OK;
+}
+
+// A sequence a context of capacity cap can take: 1..cap of A/C/G/U/T.  Checked before the context
+// is touched.
+int check_seq(ccj_pf_ctx *c, const char *seq, int cap) {
+    if (!seq) return pf_err(c, CCJ_E_ARG, "null sequence");
+    const size_t n = strlen(seq);
+    if (n < 1) return pf_err(c, CCJ_E_ARG, "empty sequence");
+    if (n > 1023) return pf_err(c, CCJ_E_ARG, "sequence longer than 1023");
+    if (cap > 0 && n > (size_t)cap) return pf_err(c, CCJ_E_ARG, "sequence longer than the context's capacity");
+    for (const char *p = seq; *p; ++p)
+        if (!(*p == 'A' || *p == 'C' || *p == 'G' || *p == 'U' || *p == 'T'))
+            return pf_err(c, CCJ_E_ARG, "sequence must be A/C/G/U/T");
+    return CCJ_OK;
+}
+
+// encode_sequence (pair_mat.h:81-183)
+void set_seq_host(ccj_pf_ctx *c, const char *seq) {
+    c->seq = seq;
+    c->n = (int)c->seq.size();
+    c->rs = c->n + 2;
+    const int n = c->n;
     c->S.assign(n + 2, 0);
     c->S1.assign(n + 2, 0);
     for (int i = 1; i <= n; ++i) c->S[i] = c->S1[i] = (short)encode_base(c->seq[i - 1]);
@@ -514,43 +549,102 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
     c->S[0] = (short)n;
     c->S1[n + 1] = c->S1[1];
     c->S1[0] = c->S1[n];
+}
 
-    if (raw && (raw->magic != CCJ_PF_RAW_MAGIC || raw->size_bytes != sizeof(ccj_pf_raw)))
-        return pf_err(c, CCJ_E_ARG, "bad ccj_pf_raw table");
-    build_exp(c->prm, raw, c->pen, c->E);
-    // exp_params_rescale (part_func.cc:97-125), pf_scale == 1 so every scale[] is 1
-    c->mlb.assign(n + 2, 0);
-    c->cpp.assign(n + 2, 0);
-    c->pup.assign(n + 2, 0);
+// exp_params_rescale (part_func.cc:97-125), pf_scale == 1 so every scale[] is 1: entry i does not
+// depend on the length, so the tables of the capacity serve every binding
+void build_powers(ccj_pf_ctx *c, int N) {
+    c->mlb.assign(N + 2, 0);
+    c->cpp.assign(N + 2, 0);
+    c->pup.assign(N + 2, 0);
     c->mlb[0] = 1;
     c->mlb[1] = c->E.MLbase / 1.;
     c->cpp[0] = 1;
     c->cpp[1] = c->E.cp / 1.;
     c->pup[0] = 1;
     c->pup[1] = c->E.PUP / 1.;
-    for (int i = 2; i <= n; ++i) {
+    for (int i = 2; i <= N; ++i) {
         c->mlb[i] = pow(c->E.MLbase, (double)i) * 1.;
         c->cpp[i] = pow(c->E.cp, (double)i) * 1.;
         c->pup[i] = pow(c->E.PUP, (double)i) * 1.;
     }
+}
 
-    // per-sequence tables
+// The key tables of ccj_pf_setup.h for sequences up to length N: get_e_intP / get_e_stP with the
+// host's pow, one entry per key.  A loop with u1 + u2 > N - 4 fits no such sequence
+// (p+1+u1 < q-1-u2 <= N-1), so those keys stay 0 and are never gathered.
+void build_keytab(const ccj_pf_ctx &c, int N, std::vector<double> &ietab, double *esttab) {
+    ietab.assign((size_t)PF_KEYS, 0.0);
+    const int nthr = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    run_threads(PF_IEW * PF_IEW, nthr, [&](int s0, int s1) {
+        for (int s = s0; s < s1; ++s) {
+            const int u1 = s / PF_IEW, u2 = s % PF_IEW;
+            if ((u1 == 0 && u2 == 0) || u1 + u2 > N - 4) continue;  // get_e_intP's stack case is 0
+            for (int type = 1; type <= 6; ++type)
+                for (int si1 = 1; si1 <= 4; ++si1)
+                    for (int sj1 = 1; sj1 <= 4; ++sj1)
+                        for (int type2 = 1; type2 <= 6; ++type2)
+                            for (int sp1 = 1; sp1 <= 4; ++sp1)
+                                for (int sq1 = 1; sq1 <= 4; ++sq1)
+                                    ietab[(size_t)pf_ie_key(u1, u2, type, si1, sj1, type2, sp1, sq1)] =
+                                        pow(exp_E_IntLoop_pf(c.E, u1, u2, type, type2, si1, sj1, sp1, sq1), c.pen.e_intP);
+        }
+    });
+    for (int type = 0; type < 8; ++type)
+        for (int type2 = 0; type2 < 8; ++type2)
+            esttab[type * 8 + type2] = pow(exp_E_IntLoop_pf(c.E, 0, 0, type, type2, 0, 0, 0, 0), c.pen.e_stP);
+}
+
+// The per-sequence tables on the host.
+struct PfHostTabs {
+    std::vector<int8_t> pt;
+    std::vector<double> est, ieO, ieI;  // ieO / ieI compacted, with the PF_ILW tail
+    std::vector<uint32_t> mO, mI, items;
+    std::vector<long long> ifirst;
+};
+
+// k_pf_iloop reads the weights of a window row only at the row's mask bits, in ascending order:
+// store them compacted (k-th set bit -> slot k), so that a round's weights are one scalar load;
+// PF_ILW zero doubles of tail padding cover the last row's round-wide reads
+void compact_rows(std::vector<double> &v, const std::vector<uint32_t> &mk) {
+    for (size_t r = 0; r < mk.size(); ++r) {
+        double *row = v.data() + r * PF_IEW;
+        int k = 0;
+        for (int u2 = 0; u2 < PF_IEW; ++u2)
+            if (mk[r] >> u2 & 1u) row[k++] = row[u2];
+        for (; k < PF_IEW; ++k) row[k] = 0.0;
+    }
+    v.resize(v.size() + PF_ILW, 0.0);
+}
+
+// HairpinE of every interval, [w][p] (plane doubles)
+void build_hp(const ccj_pf_ctx &c, double *hp) {
+    const int n = c.n, rs = c.rs;
+    memset(hp, 0, c.plane() * sizeof(double));
+    for (int w = 0; w <= n - 1; ++w)
+        for (int p = 1; p + w <= n; ++p) hp[(size_t)w * rs + p] = hairpin_pf(c, p, p + w);
+}
+
+// The direct builder: one pow per entry (CCJ_PF_HOST_SETUP=1; the yardstick of the key tables).
+void host_tables(const ccj_pf_ctx &cx, PfHostTabs &T) {
+    const ccj_pf_ctx *c = &cx;
+    const int n = c->n, rs = c->rs;
     const size_t plane = c->plane();
-    std::vector<int8_t> pt(plane, 0);
-    c->hp.assign(plane, 0);
-    std::vector<double> est(plane, 0);
+    T.pt.assign(plane, 0);
+    T.est.assign(plane, 0);
     for (int w = 0; w <= n - 1; ++w)
         for (int p = 1; p + w <= n; ++p) {
             const size_t ix = (size_t)w * rs + p;
-            pt[ix] = (int8_t)c->ptype(p, p + w);
-            c->hp[ix] = hairpin_pf(*c, p, p + w);
+            T.pt[ix] = (int8_t)c->ptype(p, p + w);
             // get_e_stP (part_func.cc:877-884); w == 0 is never read with a nonzero factor
-            if (w >= 1 && w != 2) est[ix] = pow(compute_int_pf(*c, p, p + w, p + 1, p + w - 1), c->pen.e_stP);
+            if (w >= 1 && w != 2) T.est[ix] = pow(compute_int_pf(*c, p, p + w, p + 1, p + w - 1), c->pen.e_stP);
         }
     // ieO / ieI: get_e_intP by outer / inner pair, each pair's 29 x 29 window contiguous
     constexpr int W2 = PF_IEW * PF_IEW;
     const size_t ie_n = (size_t)W2 * plane;
-    std::vector<double> ie(ie_n, 0.0), ieI(ie_n, 0.0);
+    std::vector<double> &ie = T.ieO, &ieI = T.ieI;
+    ie.assign(ie_n, 0.0);
+    ieI.assign(ie_n, 0.0);
     {
         const int nthr = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         run_threads(n, nthr, [&](int w0, int w1) {
@@ -580,7 +674,9 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
     }
     // window masks: a term adds nothing when its weight is 0.0 or the pair of the 4-D value it reads
     // cannot pair (that value is 0): mO over (p+1+u1, p+w-1-u2), mI over (j-1-u1, j+g+1+u2)
-    std::vector<uint32_t> mO(plane * PF_IEW, 0u), mI(plane * PF_IEW, 0u);
+    std::vector<uint32_t> &mO = T.mO, &mI = T.mI;
+    mO.assign(plane * PF_IEW, 0u);
+    mI.assign(plane * PF_IEW, 0u);
     for (int w = 0; w <= n - 1; ++w)
         for (int p = 1; p + w <= n; ++p)
             for (int u1 = 0; u1 < PF_IEW; ++u1) {
@@ -597,64 +693,142 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
                     }
                 }
             }
+    compact_rows(ie, mO);
+    compact_rows(ieI, mI);
+    // k_pf_iloop work items: the cells of each pairing closing pair in 64-lane chunks, encoded as
+    // ccj_items.h's (unsharded).  PL and PR rows are the MFE engine's; PM rows here start at h = 0,
+    // since get_PMiloop has no hairpin bound on (j, k) (part_func.cc:804-824)
+    std::vector<uint32_t> &items = T.items;
+    items.clear();
+    T.ifirst.assign(std::max(n - 1, 2), 0);
+    struct PT {
+        const int8_t *p;
+        int rs;
+        int operator()(int i, int j) const { return p[(size_t)(j - i) * rs + i]; }
+    } ptf{T.pt.data(), rs};
+    for (int t = 0; t <= n - 3; ++t) {
+        T.ifirst[t] = (long long)items.size();
+        const ItemRows R = item_rows(n, t, 1, 0);
+        for (int x = 0; x < R.nPL + R.nPR; ++x) {
+            uint32_t it0 = 0;
+            const int cnt = item_row(ptf, n, t, R, x, 1, 0, it0);
+            for (int q = 0; q < cnt; ++q) items.push_back(it0 | (uint32_t)q);
+        }
+        for (int h = 0; h <= R.m - 1; ++h)  // PM: pair (j, k = j+h+2), lanes a in [alo, ahi]
+            for (int j = 1; j + h + 2 <= n; ++j) {
+                const int k = j + h + 2, alo = std::max(2, t - (n - k)), ahi = std::min(t - 2, j - 1);
+                if (alo > ahi || ptf(j, k) <= 0) continue;
+                const uint32_t it0 = (2u << 30) | ((uint32_t)h << 20) | ((uint32_t)j << 10);
+                for (int q = 0; q <= (ahi - alo) / 64; ++q) items.push_back(it0 | (uint32_t)q);
+            }
+    }
+    T.ifirst[std::max(n - 2, 1)] = (long long)items.size();
+}
 
-    // level layout
-    c->lv.assign(std::max(n - 2, 1), PfLvl{0, 0, 0, 0, 0, 0, 0});
-    long long off = 0, offx = 0, offm = 0, maxC = 1;
+// The same tables through the key tables and the gathers of ccj_pf_setup.h, as the setup kernels
+// form them (row by row: mask, then the set bits' weights in ascending order).  Rows of intervals
+// that cannot pair are zero here, which the fill never reads (k_pf_iloop has no item for them).
+void keyed_tables(const ccj_pf_ctx &c, const double *ietab, const double *esttab, PfHostTabs &T) {
+    const int n = c.n, rs = c.rs;
+    const size_t plane = c.plane();
+    int8_t pair8[64], rt8[8];
+    for (int x = 0; x < 8; ++x) {
+        rt8[x] = (int8_t)c.rtype[x];
+        for (int y = 0; y < 8; ++y) pair8[x * 8 + y] = (int8_t)c.pair[x][y];
+    }
+    const PfSeqView v{n, rs, c.S.data(), pair8, rt8, ietab, esttab};
+    constexpr int W2 = PF_IEW * PF_IEW;
+    T.pt.assign(plane, 0);
+    T.est.assign(plane, 0);
+    T.ieO.assign(W2 * plane + PF_ILW, 0.0);
+    T.ieI.assign(W2 * plane + PF_ILW, 0.0);
+    T.mO.assign(plane * PF_IEW, 0u);
+    T.mI.assign(plane * PF_IEW, 0u);
+    for (int w = 0; w <= n - 1; ++w)
+        for (int p = 1; p + w <= n; ++p) {
+            const size_t ix = (size_t)w * rs + p;
+            T.pt[ix] = (int8_t)v.ptype(p, p + w);
+            T.est[ix] = pf_est_gather(v, w, p);
+            for (int u1 = 0; u1 < PF_IEW; ++u1) {
+                const size_t r = ix * PF_IEW + u1;
+                int kO = 0, kI = 0;
+                for (int u2 = 0; u2 < PF_IEW; ++u2) {
+                    double wt;
+                    if (pf_ie_outer(v, w, p, u1, u2, wt)) {
+                        T.mO[r] |= 1u << u2;
+                        T.ieO[r * PF_IEW + kO++] = wt;
+                    }
+                    if (pf_ie_inner(v, w, p, u1, u2, wt)) {
+                        T.mI[r] |= 1u << u2;
+                        T.ieI[r * PF_IEW + kI++] = wt;
+                    }
+                }
+            }
+        }
+}
+
+// FNV hashes of the setup tables: est whole; per interval whose pair can pair, in [w][p] order,
+// the 29 mask words and the 29 x 29 compacted weights of ieO / mO and of ieI / mI.
+void setup_table_hashes(const ccj_pf_ctx &c, const int8_t *pt, const double *est, const double *ieO, const double *ieI,
+                        const uint32_t *mO, const uint32_t *mI, uint64_t *out5) {
+    const int n = c.n, rs = c.rs;
+    constexpr int W2 = PF_IEW * PF_IEW;
+    out5[0] = fnv_arr(est, c.plane());
+    uint64_t h[4] = {fnv_init(), fnv_init(), fnv_init(), fnv_init()};
+    for (int w = 0; w <= n - 1; ++w)
+        for (int p = 1; p + w <= n; ++p) {
+            const size_t ix = (size_t)w * rs + p;
+            if (pt[ix] <= 0) continue;
+            fnv_bytes(h[0], ieO + ix * W2, W2 * sizeof(double));
+            fnv_bytes(h[1], ieI + ix * W2, W2 * sizeof(double));
+            fnv_bytes(h[2], mO + ix * PF_IEW, PF_IEW * sizeof(uint32_t));
+            fnv_bytes(h[3], mI + ix * PF_IEW, PF_IEW * sizeof(uint32_t));
+        }
+    for (int q = 0; q < 4; ++q) out5[1 + q] = h[q];
+}
+
+// Level layout of a length (ccj_pf_engine.h).  Fails where k_pf_ppush's offsets would not fit.
+struct PfLayout {
+    std::vector<PfLvl> lv;
+    long long cells = 0, off = 0, offx = 0, offm = 0, maxC = 1;
+};
+bool make_layout(int n, PfLayout &Y) {
+    Y = PfLayout{};
+    Y.lv.assign(std::max(n - 2, 1), PfLvl{0, 0, 0, 0, 0, 0, 0});
     for (int t = 0; t <= n - 3; ++t) {
         const long long m = n - t - 2, M = m * (m + 1) / 2;
-        c->lv[t] = PfLvl{off, (t + 1) * M, (int)M, 0, offx, offm, c->cells};
-        off += (long long)PF_NMAT4 * (t + 1) * M;
-        offx += 2 * (t + 1) * M;
-        offm += m * n * (t + 1);
-        maxC = std::max(maxC, (t + 1) * M);
-        c->cells += (t + 1) * M;
+        Y.lv[t] = PfLvl{Y.off, (t + 1) * M, (int)M, 0, Y.offx, Y.offm, Y.cells};
+        Y.off += (long long)PF_NMAT4 * (t + 1) * M;
+        Y.offx += 2 * (t + 1) * M;
+        Y.offm += m * n * (t + 1);
+        Y.maxC = std::max(Y.maxC, (t + 1) * M);
+        Y.cells += (t + 1) * M;
     }
     // k_pf_ppush addresses the PK rows of PF_PP_S consecutive levels as 32-bit byte offsets from the
     // lowest one's PK start (one buffer resource per wave): that span must stay below 4 GB
     for (int t = 0; t <= n - 3; ++t) {
         const int tt = std::min(t + PF_PP_S - 1, n - 3);
-        const long long lo = c->lv[t].lb + PF_PK * c->lv[t].C, hi = c->lv[tt].lb + PF_PK * c->lv[tt].C + c->lv[tt].C;
-        if (4 * (hi - lo) >= (1LL << 32)) return pf_err(c, CCJ_E_ARG, "n too large: the PK rows of 8 levels exceed 4 GB (k_pf_ppush offsets)");
+        const long long lo = Y.lv[t].lb + PF_PK * Y.lv[t].C, hi = Y.lv[tt].lb + PF_PK * Y.lv[tt].C + Y.lv[tt].C;
+        if (4 * (hi - lo) >= (1LL << 32)) return false;
     }
-    // k_pf_iloop work items: the cells of each pairing closing pair in 64-lane chunks, encoded as
-    // ccj_items.h's (unsharded).  PL and PR rows are the MFE engine's; PM rows here start at h = 0,
-    // since get_PMiloop has no hairpin bound on (j, k) (part_func.cc:804-824)
-    std::vector<uint32_t> items;
-    c->ifirst.assign(std::max(n - 1, 2), 0);
-    {
-        struct PT {
-            const int8_t *p;
-            int rs;
-            int operator()(int i, int j) const { return p[(size_t)(j - i) * rs + i]; }
-        } ptf{pt.data(), rs};
-        for (int t = 0; t <= n - 3; ++t) {
-            c->ifirst[t] = (long long)items.size();
-            const ItemRows R = item_rows(n, t, 1, 0);
-            for (int x = 0; x < R.nPL + R.nPR; ++x) {
-                uint32_t it0 = 0;
-                const int cnt = item_row(ptf, n, t, R, x, 1, 0, it0);
-                for (int q = 0; q < cnt; ++q) items.push_back(it0 | (uint32_t)q);
-            }
-            for (int h = 0; h <= R.m - 1; ++h)  // PM: pair (j, k = j+h+2), lanes a in [alo, ahi]
-                for (int j = 1; j + h + 2 <= n; ++j) {
-                    const int k = j + h + 2, alo = std::max(2, t - (n - k)), ahi = std::min(t - 2, j - 1);
-                    if (alo > ahi || ptf(j, k) <= 0) continue;
-                    const uint32_t it0 = (2u << 30) | ((uint32_t)h << 20) | ((uint32_t)j << 10);
-                    for (int q = 0; q <= (ahi - alo) / 64; ++q) items.push_back(it0 | (uint32_t)q);
-                }
-        }
-        c->ifirst[std::max(n - 2, 1)] = (long long)items.size();
-    }
+    return true;
+}
+const char *const kPpushMsg = "n too large: the PK rows of 8 levels exceed 4 GB (k_pf_ppush offsets)";
 
-    // device
+// Allocation for a capacity N: every buffer, event and pinned staging area at its maximum over the
+// lengths 1..N.  Each size grows with the length, so the layout of N gives the maxima.
+int alloc_cap(ccj_pf_ctx *c, int N, int device, const PfLayout &Y) {
+    c->cap = N;
+    c->device = device;
+    const size_t plane = (size_t)(N + 1) * (N + 2);
+    constexpr int W2 = PF_IEW * PF_IEW;
     PFCHK(c, hipSetDevice(device));
     PFCHK(c, hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
     PFCHK(c, hipStreamCreateWithFlags(&c->st_il, hipStreamNonBlocking));
     PFCHK(c, hipStreamCreateWithFlags(&c->st_d, hipStreamNonBlocking));
     PFCHK(c, hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming));
     for (auto *v : {&c->ev_lev, &c->ev_il, &c->ev_dg}) {
-        v->assign(n + 1, nullptr);
+        v->assign(N + 1, nullptr);
         for (hipEvent_t &e : *v) PFCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     PFCHK(c, hipEventCreate(&c->e0));
@@ -669,57 +843,54 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
         rt8[x] = (int8_t)c->rtype[x];
         for (int y = 0; y < 8; ++y) pair8[x * 8 + y] = (int8_t)c->pair[x][y];
     }
+    // once per context: the model's tables
     PFCHK(c, up((void **)&c->d_E, &c->E, sizeof(PfExp)));
-    PFCHK(c, up((void **)&c->d_S, c->S.data(), c->S.size() * sizeof(short)));
-    PFCHK(c, up((void **)&c->d_S1, c->S1.data(), c->S1.size() * sizeof(short)));
-    PFCHK(c, up((void **)&c->d_pt, pt.data(), pt.size()));
     PFCHK(c, up((void **)&c->d_pair, pair8, 64));
     PFCHK(c, up((void **)&c->d_rtype, rt8, 8));
-    PFCHK(c, up((void **)&c->d_hp, c->hp.data(), plane * sizeof(double)));
-    PFCHK(c, up((void **)&c->d_est, est.data(), plane * sizeof(double)));
-    // k_pf_iloop reads the weights of a window row only at the row's mask bits, in ascending order:
-    // store them compacted (k-th set bit -> slot k), so that a round's weights are one scalar load;
-    // PF_ILW zero doubles of tail padding cover the last row's round-wide reads
-    auto compact = [&](std::vector<double> &v, const std::vector<uint32_t> &mk) {
-        for (size_t r = 0; r < mk.size(); ++r) {
-            double *row = v.data() + r * PF_IEW;
-            int k = 0;
-            for (int u2 = 0; u2 < PF_IEW; ++u2)
-                if (mk[r] >> u2 & 1u) row[k++] = row[u2];
-            for (; k < PF_IEW; ++k) row[k] = 0.0;
-        }
-        v.resize(v.size() + PF_ILW, 0.0);
-    };
-    compact(ie, mO);
-    compact(ieI, mI);
-    PFCHK(c, up((void **)&c->d_ieO, ie.data(), ie.size() * sizeof(double)));
-    PFCHK(c, up((void **)&c->d_ieI, ieI.data(), ieI.size() * sizeof(double)));
-    PFCHK(c, up((void **)&c->d_items, items.data(), items.size() * sizeof(uint32_t)));
-    PFCHK(c, up((void **)&c->d_mO, mO.data(), mO.size() * sizeof(uint32_t)));
-    PFCHK(c, up((void **)&c->d_mI, mI.data(), mI.size() * sizeof(uint32_t)));
-    c->h_items = std::move(items);
-    c->h_mO = std::move(mO);
-    c->h_mI = std::move(mI);
     PFCHK(c, up((void **)&c->d_mlb, c->mlb.data(), c->mlb.size() * sizeof(double)));
     PFCHK(c, up((void **)&c->d_cpp, c->cpp.data(), c->cpp.size() * sizeof(double)));
     PFCHK(c, up((void **)&c->d_pup, c->pup.data(), c->pup.size() * sizeof(double)));
-    PFCHK(c, up((void **)&c->d_ld, c->lv.data(), c->lv.size() * sizeof(PfLvl)));
+    {
+        std::vector<double> ietab;
+        const auto t0 = std::chrono::steady_clock::now();
+        build_keytab(*c, N, ietab, c->esttab);
+        c->keytab_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        PFCHK(c, up((void **)&c->d_ietab, ietab.data(), ietab.size() * sizeof(double)));
+        PFCHK(c, up((void **)&c->d_esttab, c->esttab, sizeof c->esttab));
+    }
+    // per sequence
+    PFCHK(c, hipMalloc((void **)&c->d_S, (size_t)(N + 2) * sizeof(short)));
+    PFCHK(c, hipMalloc((void **)&c->d_S1, (size_t)(N + 2) * sizeof(short)));
+    PFCHK(c, hipMalloc((void **)&c->d_pt, plane));
+    PFCHK(c, hipMalloc((void **)&c->d_hp, plane * sizeof(double)));
+    PFCHK(c, hipMalloc((void **)&c->d_est, plane * sizeof(double)));
+    PFCHK(c, hipMalloc((void **)&c->d_ieO, (W2 * plane + PF_ILW) * sizeof(double)));
+    PFCHK(c, hipMalloc((void **)&c->d_ieI, (W2 * plane + PF_ILW) * sizeof(double)));
+    PFCHK(c, hipMalloc((void **)&c->d_mO, plane * PF_IEW * sizeof(uint32_t)));
+    PFCHK(c, hipMalloc((void **)&c->d_mI, plane * PF_IEW * sizeof(uint32_t)));
+    c->items_cap = (long long)pf_items_bound(N);
+    PFCHK(c, hipMalloc((void **)&c->d_items, (size_t)std::max(c->items_cap, 2LL) * sizeof(uint32_t)));
+    const size_t nsp = (size_t)std::max(N - 2, 1) * KI_SPLIT;
+    PFCHK(c, hipMalloc((void **)&c->d_icount, nsp * sizeof(long long)));
+    PFCHK(c, hipMalloc((void **)&c->d_ioff, nsp * sizeof(long long)));
+    PFCHK(c, hipMalloc((void **)&c->d_ld, Y.lv.size() * sizeof(PfLvl)));
+    // per fill
     PFCHK(c, hipMalloc((void **)&c->d_2d, (size_t)CCJ_PF_NMAT2 * plane * sizeof(double)));
     PFCHK(c, hipMalloc((void **)&c->d_Pacc, plane * sizeof(long long)));
     PFCHK(c, hipMalloc((void **)&c->d_Pabs, plane * sizeof(unsigned long long)));
-    PFCHK(c, hipMalloc((void **)&c->d_d4, (size_t)std::max(off, 1LL) * sizeof(int)));
-    PFCHK(c, hipMalloc((void **)&c->d_prec, (size_t)PF_RECS * std::max(c->cells, 1LL) * sizeof(int)));
-    // the copies stay 0 where the pair cannot pair (never written): set once per context
-    PFCHK(c, hipMalloc((void **)&c->d_cx, (size_t)std::max(offx, 1LL) * sizeof(int)));
-    PFCHK(c, hipMalloc((void **)&c->d_pmx, (size_t)std::max(offm, 1LL) * sizeof(int)));
-    PFCHK(c, hipMemset(c->d_cx, 0, (size_t)std::max(offx, 1LL) * sizeof(int)));
-    PFCHK(c, hipMemset(c->d_pmx, 0, (size_t)std::max(offm, 1LL) * sizeof(int)));
-    PFCHK(c, hipMalloc((void **)&c->d_R, (size_t)2 * 3 * maxC * sizeof(double)));
-    c->D.Rst = 3 * maxC;
+    PFCHK(c, hipMalloc((void **)&c->d_d4, (size_t)std::max(Y.off, 1LL) * sizeof(int)));
+    PFCHK(c, hipMalloc((void **)&c->d_prec, (size_t)PF_RECS * std::max(Y.cells, 1LL) * sizeof(int)));
+    PFCHK(c, hipMalloc((void **)&c->d_cx, (size_t)std::max(Y.offx, 1LL) * sizeof(int)));
+    PFCHK(c, hipMalloc((void **)&c->d_pmx, (size_t)std::max(Y.offm, 1LL) * sizeof(int)));
+    PFCHK(c, hipMalloc((void **)&c->d_R, (size_t)2 * 3 * Y.maxC * sizeof(double)));
+    // pinned staging
+    PFCHK(c, hipHostMalloc((void **)&c->h_S, (size_t)2 * (N + 2) * sizeof(short)));
+    PFCHK(c, hipHostMalloc((void **)&c->h_hp, plane * sizeof(double)));
+    PFCHK(c, hipHostMalloc((void **)&c->h_lv, Y.lv.size() * sizeof(PfLvl)));
+    PFCHK(c, hipHostMalloc((void **)&c->h_icount, nsp * sizeof(long long)));
+    PFCHK(c, hipHostMalloc((void **)&c->h_ioff, nsp * sizeof(long long)));
 
     PfDev &D = c->D;
-    D.n = n;
-    D.rs = rs;
     D.dangles = c->dangles;
     D.ap_int = c->pen.ap;
     D.E = c->d_E;
@@ -737,6 +908,33 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
     D.mlb = c->d_mlb;
     D.cpp = c->d_cpp;
     D.pup = c->d_pup;
+    D.Pacc = c->d_Pacc;
+    D.Pabs = c->d_Pabs;
+    D.d4 = c->d_d4;
+    D.cx = c->d_cx;
+    D.pmx = c->d_pmx;
+    D.items = c->d_items;
+    D.R = c->d_R;
+    D.ld = c->d_ld;
+    return CCJ_OK;
+}
+
+// Bind the length of c->seq (set_seq_host): the row stride and the plane bases inside d_2d, the
+// level descriptors with the record bases, Rst.  Allocates nothing; at n == capacity every offset
+// is what a context created for that length has.
+int bind_len(ccj_pf_ctx *c, const PfLayout &Y) {
+    const int n = c->n;
+    const size_t plane = c->plane();
+    c->lv = Y.lv;
+    c->cells = Y.cells;
+    c->offx = Y.offx;
+    c->offm = Y.offm;
+    memcpy(c->h_lv, c->lv.data(), c->lv.size() * sizeof(PfLvl));
+    PFCHK(c, hipMemcpyAsync(c->d_ld, c->h_lv, c->lv.size() * sizeof(PfLvl), hipMemcpyHostToDevice, c->st));
+    PfDev &D = c->D;
+    D.n = n;
+    D.rs = c->rs;
+    D.Rst = 3 * Y.maxC;
     double *pl[CCJ_PF_NMAT2];
     for (int m = 0; m < CCJ_PF_NMAT2; ++m) pl[m] = c->d_2d + (size_t)m * plane;
     D.V = pl[CCJ_PF_V];
@@ -747,19 +945,156 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_
     D.WBP = pl[CCJ_PF_WBP];
     D.WPP = pl[CCJ_PF_WPP];
     D.P = pl[CCJ_PF_P];
-    D.Pacc = c->d_Pacc;
-    D.Pabs = c->d_Pabs;
-    D.d4 = c->d_d4;
     D.r1 = c->d_prec;
     D.r2 = D.r1 + (size_t)PF_REC1 * c->cells;
     D.r3 = D.r2 + (size_t)PF_REC2 * c->cells;
     D.r4 = D.r3 + (size_t)PF_REC3 * c->cells;
-    D.cx = c->d_cx;
-    D.pmx = c->d_pmx;
-    D.items = c->d_items;
-    D.R = c->d_R;
-    D.ld = c->d_ld;
     return CCJ_OK;
+}
+
+bool host_setup() {
+    const char *e = getenv("CCJ_PF_HOST_SETUP");
+    return e && atoi(e) != 0;
+}
+
+// The per-sequence state of the bound sequence, on the context's stream: S / S1 and hp (host,
+// through pinned staging), the copies zeroed, then pt, est, ieO / ieI, mO / mI and the work items
+// by the setup kernels (ccj_pf.hip).  One wait: the item counts, whose prefix the host forms.
+// CCJ_PF_HOST_SETUP=1: the tables of host_tables() instead, uploaded with blocking copies.
+int setup_seq(ccj_pf_ctx *c) {
+    const int n = c->n, N2 = c->cap + 2;
+    const size_t plane = c->plane();
+    constexpr int W2 = PF_IEW * PF_IEW;
+    c->filled = false;
+    c->h_items.clear();
+    c->h_mO.clear();
+    c->h_mI.clear();
+    PFCHK(c, hipSetDevice(c->device));
+    memcpy(c->h_S, c->S.data(), (size_t)(n + 2) * sizeof(short));
+    memcpy(c->h_S + N2, c->S1.data(), (size_t)(n + 2) * sizeof(short));
+    PFCHK(c, hipMemcpyAsync(c->d_S, c->h_S, (size_t)(n + 2) * sizeof(short), hipMemcpyHostToDevice, c->st));
+    PFCHK(c, hipMemcpyAsync(c->d_S1, c->h_S + N2, (size_t)(n + 2) * sizeof(short), hipMemcpyHostToDevice, c->st));
+    // The copies of PL / PR / PM are written only where the pair can pair and read as 0 elsewhere;
+    // which pairs can pair changes with the sequence: zero the bound extent (DESIGN.md §10 audit)
+    PFCHK(c, hipMemsetAsync(c->d_cx, 0, (size_t)std::max(c->offx, 1LL) * sizeof(int), c->st));
+    PFCHK(c, hipMemsetAsync(c->d_pmx, 0, (size_t)std::max(c->offm, 1LL) * sizeof(int), c->st));
+    c->ifirst.assign(std::max(n - 1, 2), 0);
+    if (host_setup()) {
+        build_hp(*c, c->h_hp);
+        PFCHK(c, hipMemcpyAsync(c->d_hp, c->h_hp, plane * sizeof(double), hipMemcpyHostToDevice, c->st));
+        PfHostTabs T;
+        host_tables(*c, T);
+        if ((long long)T.items.size() > c->items_cap) return pf_err(c, CCJ_E_STATE, "work items exceed their bound");
+        PFCHK(c, hipStreamSynchronize(c->st));
+        PFCHK(c, hipMemcpy(c->d_pt, T.pt.data(), T.pt.size(), hipMemcpyHostToDevice));
+        PFCHK(c, hipMemcpy(c->d_est, T.est.data(), T.est.size() * sizeof(double), hipMemcpyHostToDevice));
+        PFCHK(c, hipMemcpy(c->d_ieO, T.ieO.data(), T.ieO.size() * sizeof(double), hipMemcpyHostToDevice));
+        PFCHK(c, hipMemcpy(c->d_ieI, T.ieI.data(), T.ieI.size() * sizeof(double), hipMemcpyHostToDevice));
+        PFCHK(c, hipMemcpy(c->d_mO, T.mO.data(), T.mO.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        PFCHK(c, hipMemcpy(c->d_mI, T.mI.data(), T.mI.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (!T.items.empty())
+            PFCHK(c, hipMemcpy(c->d_items, T.items.data(), T.items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        c->ifirst = T.ifirst;
+        return CCJ_OK;
+    }
+    PfSetupDev T;
+    T.v = PfSeqView{n, c->rs, c->d_S, c->d_pair, c->d_rtype, c->d_ietab, c->d_esttab};
+    T.pt = c->d_pt;
+    T.est = c->d_est;
+    T.ieO = c->d_ieO;
+    T.ieI = c->d_ieI;
+    T.mO = c->d_mO;
+    T.mI = c->d_mI;
+    PFCHK(c, (hipError_t)ccjk_pf_setup_tables(&T, c->st));
+    PFCHK(c, hipMemsetAsync(c->d_ieO + W2 * plane, 0, PF_ILW * sizeof(double), c->st));
+    PFCHK(c, hipMemsetAsync(c->d_ieI + W2 * plane, 0, PF_ILW * sizeof(double), c->st));
+    const int nl = std::max(n - 2, 0);
+    const size_t nsp = (size_t)nl * KI_SPLIT;
+    if (nsp) {
+        PFCHK(c, (hipError_t)ccjk_pf_items(&T, c->d_icount, nullptr, nullptr, 0, c->st));
+        PFCHK(c, hipMemcpyAsync(c->h_icount, c->d_icount, nsp * sizeof(long long), hipMemcpyDeviceToHost, c->st));
+    }
+    // hp: the special-hairpin strstr cases stay on the host; built while the kernels run
+    build_hp(*c, c->h_hp);
+    PFCHK(c, hipMemcpyAsync(c->d_hp, c->h_hp, plane * sizeof(double), hipMemcpyHostToDevice, c->st));
+    PFCHK(c, hipStreamSynchronize(c->st));  // the one wait of a reset: the item counts
+    long long o = 0;
+    for (int t = 0; t < nl; ++t) {
+        c->ifirst[t] = o;
+        for (int s = 0; s < KI_SPLIT; ++s) {
+            c->h_ioff[(size_t)t * KI_SPLIT + s] = o;
+            o += c->h_icount[(size_t)t * KI_SPLIT + s];
+        }
+    }
+    c->ifirst[std::max(n - 2, 1)] = o;
+    if (o > c->items_cap) return pf_err(c, CCJ_E_STATE, "work items exceed their bound");
+    if (nsp) {
+        PFCHK(c, hipMemcpyAsync(c->d_ioff, c->h_ioff, nsp * sizeof(long long), hipMemcpyHostToDevice, c->st));
+        PFCHK(c, (hipError_t)ccjk_pf_items(&T, nullptr, c->d_ioff, c->d_items, 1, c->st));
+    }
+    return CCJ_OK;
+}
+
+// Rebind an open context to seq (any length up to the capacity; the bound length = a reset).
+int rebind_impl(ccj_pf_ctx *c, const char *seq) {
+    const int rc = check_seq(c, seq, c->cap);
+    if (rc != CCJ_OK) return rc;
+    PfLayout Y;
+    if (!make_layout((int)strlen(seq), Y)) return pf_err(c, CCJ_E_ARG, kPpushMsg);
+    set_seq_host(c, seq);
+    PFCHK(c, hipSetDevice(c->device));
+    const int rb = bind_len(c, Y);
+    return rb != CCJ_OK ? rb : setup_seq(c);
+}
+
+int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int N, ccj_pf_ctx *c) {
+    // N > 0: a capacity context, bound to prob->seq when it has one, else to poly-A of length N
+    if (!prob) return pf_err(c, CCJ_E_ARG, "null problem");
+    std::string seq = prob->seq ? prob->seq : "";
+    if (N <= 0) N = (int)seq.size();
+    else if (seq.empty()) seq.assign((size_t)std::min(N, 1023), 'A');
+    if (N > 1023) return pf_err(c, CCJ_E_ARG, "sequence longer than 1023");
+    int rc = check_seq(c, seq.c_str(), N);
+    if (rc == CCJ_OK) rc = init_model(prob, raw, c);
+    if (rc != CCJ_OK) return rc;
+    {
+        // Size check before any table is built (ccj_pf_footprint: the allocations below, summed).
+        // Past what the GPU (or, for the host builder, the host) can hold, fail with CCJ_E_OOM up
+        // front.  CCJ_PF_DEVMEM_LIMIT (bytes) stands in for the device's free memory (tests pin the
+        // accept/reject boundary with it).
+        unsigned long long dev_b = 0, host_b = 0;
+        ccj_pf_footprint(N, &dev_b, &host_b);
+        size_t dfree = 0, dtotal = 0;
+        char msg[200];
+        const char *lim = getenv("CCJ_PF_DEVMEM_LIMIT");
+        if (lim && *lim) dfree = (size_t)strtoull(lim, nullptr, 10);
+        else if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&dfree, &dtotal) != hipSuccess) dfree = SIZE_MAX;
+        if ((double)dev_b > (double)dfree) {
+            snprintf(msg, sizeof msg, "n=%d needs ~%.1f GB of device memory, %.1f GB free", N, dev_b / 1e9, dfree / 1e9);
+            return pf_err(c, CCJ_E_OOM, msg);
+        }
+        // MemAvailable counts reclaimable page cache (sysconf(_SC_AVPHYS_PAGES) does not)
+        unsigned long long avail_kb = 0;
+        if (host_setup())
+            if (FILE *f = fopen("/proc/meminfo", "r")) {
+                char line[256];
+                while (fgets(line, sizeof line, f))
+                    if (sscanf(line, "MemAvailable: %llu kB", &avail_kb) == 1) break;
+                fclose(f);
+            }
+        if (avail_kb > 0 && (double)host_b > (double)avail_kb * 1024.0) {
+            snprintf(msg, sizeof msg, "n=%d needs ~%.1f GB of host memory for the interior-loop tables", N, host_b / 1e9);
+            return pf_err(c, CCJ_E_OOM, msg);
+        }
+    }
+    PfLayout YN, Y;
+    if (!make_layout(N, YN) || !make_layout((int)seq.size(), Y)) return pf_err(c, CCJ_E_ARG, kPpushMsg);
+    build_powers(c, N);
+    rc = alloc_cap(c, N, device, YN);
+    if (rc != CCJ_OK) return rc;
+    set_seq_host(c, seq.c_str());
+    rc = bind_len(c, Y);
+    return rc != CCJ_OK ? rc : setup_seq(c);
 }
 
 int fill_impl(ccj_pf_ctx *c) {
@@ -1143,7 +1478,7 @@ int exp_hashes(const PfExp &P, const ccj_energy_params &prm, uint64_t *out);
 
 extern "C" {
 
-int ccj_pf_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_pf_ctx **out) {
+static int create_any(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int N, ccj_pf_ctx **out) {
     if (!out) return CCJ_E_ARG;
     *out = nullptr;
     ccj_pf_ctx *c = new (std::nothrow) ccj_pf_ctx();
@@ -1151,7 +1486,7 @@ int ccj_pf_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, cc
     initstate_r(1, c->rnd_state, sizeof c->rnd_state, &c->rnd);
     int rc;
     try {
-        rc = create_impl(prob, raw, device, c);
+        rc = create_impl(prob, raw, device, N, c);
     } catch (const std::bad_alloc &) {  // host tables: no exception crosses the C ABI
         rc = pf_err(c, CCJ_E_OOM, "host allocation failed");
     }
@@ -1162,6 +1497,106 @@ int ccj_pf_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, cc
         return rc;
     }
     *out = c;
+    return CCJ_OK;
+}
+
+int ccj_pf_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_pf_ctx **out) {
+    if (!prob || !prob->seq) return CCJ_E_ARG;
+    return create_any(prob, raw, device, 0, out);
+}
+
+int ccj_pf_create_cap(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int capacity, ccj_pf_ctx **out) {
+    if (capacity < 1) return CCJ_E_ARG;
+    return create_any(prob, raw, device, capacity, out);
+}
+
+int ccj_pf_rebind(ccj_pf_ctx *c, const char *seq) {
+    if (!c) return CCJ_E_ARG;
+    try {
+        return rebind_impl(c, seq);
+    } catch (const std::bad_alloc &) {
+        return pf_err(c, CCJ_E_OOM, "host allocation failed");
+    }
+}
+
+int ccj_pf_reset(ccj_pf_ctx *c, const char *seq) {
+    if (!c) return CCJ_E_ARG;
+    if (!seq || strlen(seq) != (size_t)c->n) return pf_err(c, CCJ_E_ARG, "ccj_pf_reset: the sequence must have the bound length");
+    return ccj_pf_rebind(c, seq);
+}
+
+int ccj_pf_capacity(const ccj_pf_ctx *c) { return c ? c->cap : 0; }
+int ccj_pf_n(const ccj_pf_ctx *c) { return c ? c->n : 0; }
+
+int ccj_pf_keytab_info(const ccj_pf_ctx *c, double *build_ms, unsigned long long *bytes) {
+    if (!c) return CCJ_E_ARG;
+    if (build_ms) *build_ms = c->keytab_ms;
+    if (bytes) *bytes = (unsigned long long)PF_KEYS * sizeof(double) + sizeof c->esttab;
+    return CCJ_OK;
+}
+
+// pt, est, hp, items (with ifirst), then per pairing interval ieO, ieI, mO, mI: 8 hashes of the
+// bound sequence's setup tables as they stand on the device.
+int ccj_pf_setup_hashes(ccj_pf_ctx *c, uint64_t *out, int cap) {
+    if (!c || !out || cap < 8) return CCJ_E_ARG;
+    const size_t plane = c->plane();
+    constexpr size_t W2 = PF_IEW * PF_IEW;
+    try {
+        std::vector<int8_t> pt(plane);
+        std::vector<double> est(plane), hp(plane), ieO(W2 * plane), ieI(W2 * plane);
+        std::vector<uint32_t> mO(plane * PF_IEW), mI(plane * PF_IEW);
+        const long long ni = c->ifirst[std::max(c->n - 2, 1)];
+        std::vector<uint32_t> items((size_t)std::max(ni, 1LL), 0u);
+        PFCHK(c, hipSetDevice(c->device));
+        PFCHK(c, hipStreamSynchronize(c->st));
+        PFCHK(c, hipMemcpy(pt.data(), c->d_pt, plane, hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(est.data(), c->d_est, plane * sizeof(double), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(hp.data(), c->d_hp, plane * sizeof(double), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(ieO.data(), c->d_ieO, ieO.size() * sizeof(double), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(ieI.data(), c->d_ieI, ieI.size() * sizeof(double), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(mO.data(), c->d_mO, mO.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(mI.data(), c->d_mI, mI.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (ni > 0) PFCHK(c, hipMemcpy(items.data(), c->d_items, (size_t)ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        uint64_t h5[5];
+        setup_table_hashes(*c, pt.data(), est.data(), ieO.data(), ieI.data(), mO.data(), mI.data(), h5);
+        out[0] = fnv_arr(pt.data(), plane);
+        out[1] = h5[0];
+        out[2] = fnv_arr(hp.data(), plane);
+        uint64_t hi = fnv_init();
+        fnv_bytes(hi, c->ifirst.data(), c->ifirst.size() * sizeof(long long));
+        fnv_bytes(hi, items.data(), (size_t)ni * sizeof(uint32_t));
+        out[3] = hi;
+        for (int q = 0; q < 4; ++q) out[4 + q] = h5[1 + q];
+    } catch (const std::bad_alloc &) {
+        return pf_err(c, CCJ_E_OOM, "host allocation failed");
+    }
+    return CCJ_OK;
+}
+
+// Host only (no GPU): the hashes of setup_table_hashes (est, ieO, ieI, mO, mI) of a problem, built
+// with one pow per entry (direct) and through the key tables and the shared gathers (keyed).
+int ccj_pf_setup_host_hashes(const ccj_problem *prob, const ccj_pf_raw *raw, uint64_t *direct5, uint64_t *keyed5) {
+    if (!prob || !prob->seq || !direct5 || !keyed5) return CCJ_E_ARG;
+    try {
+        ccj_pf_ctx c;
+        int rc = check_seq(&c, prob->seq, 0);
+        if (rc == CCJ_OK) rc = init_model(prob, raw, &c);
+        if (rc != CCJ_OK) return rc;
+        set_seq_host(&c, prob->seq);
+        {
+            PfHostTabs T;
+            host_tables(c, T);
+            setup_table_hashes(c, T.pt.data(), T.est.data(), T.ieO.data(), T.ieI.data(), T.mO.data(), T.mI.data(), direct5);
+        }
+        std::vector<double> ietab;
+        double esttab[64];
+        build_keytab(c, c.n, ietab, esttab);
+        PfHostTabs T;
+        keyed_tables(c, ietab.data(), esttab, T);
+        setup_table_hashes(c, T.pt.data(), T.est.data(), T.ieO.data(), T.ieI.data(), T.mO.data(), T.mI.data(), keyed5);
+    } catch (const std::bad_alloc &) {
+        return CCJ_E_OOM;
+    }
     return CCJ_OK;
 }
 
@@ -1367,6 +1802,18 @@ int ccj_pf_kernel_ms(ccj_pf_ctx *c, double *ms4) {
 
 int ccj_pf_work_model(ccj_pf_ctx *c, double *bytes4) {
     if (!c || !bytes4) return CCJ_E_ARG;
+    if (c->h_mO.empty()) {  // the items and masks live on the device: fetched on demand, kept until the next setup
+        const size_t nm = c->plane() * PF_IEW;
+        const long long ni = c->ifirst[std::max(c->n - 2, 1)];
+        c->h_items.assign((size_t)std::max(ni, 1LL), 0u);
+        c->h_mO.assign(nm, 0u);
+        c->h_mI.assign(nm, 0u);
+        PFCHK(c, hipSetDevice(c->device));
+        PFCHK(c, hipStreamSynchronize(c->st));
+        if (ni > 0) PFCHK(c, hipMemcpy(c->h_items.data(), c->d_items, (size_t)ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(c->h_mO.data(), c->d_mO, nm * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        PFCHK(c, hipMemcpy(c->h_mI.data(), c->d_mI, nm * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
     const PfWork w = pf_work_model(*c);
     bytes4[0] = w.iloop;
     bytes4[1] = w.level;

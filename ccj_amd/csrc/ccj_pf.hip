@@ -1153,3 +1153,113 @@ extern "C" int ccjk_pf_canon(const PfDev *D, int x, const long long *rowoff, int
                        nrows, out);
     return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Per-sequence setup (ccj_pf_reset / ccj_pf_rebind): pt, est, the compacted weight
+// windows ieO / ieI with their masks, and the k_pf_iloop work items, all as gathers from the
+// context's host-built key tables (ccj_pf_setup.h) — no transcendental runs here.
+// ---------------------------------------------------------------------------------------------
+#include "ccj_items.h"
+#include "ccj_pf_setup.h"
+
+namespace {
+
+// pt and est over the whole bound plane (0 outside the triangle, like the host builder)
+__global__ __launch_bounds__(256) void k_pf_seq_tables(PfSetupDev T) {
+    const int n = T.v.n, rs = T.v.rs;
+    const int ix = blockIdx.x * 256 + threadIdx.x;
+    if (ix >= (n + 1) * rs) return;
+    const int w = ix / rs, p = ix - w * rs;
+    T.pt[ix] = (p >= 1 && p + w <= n) ? (int8_t)T.v.ptype(p, p + w) : (int8_t)0;
+    T.est[ix] = pf_est_gather(T.v, w, p);
+}
+
+// One half-wave per window row (table O or I, interval (w, p), u1), lane u2: gather the weight,
+// ballot the mask, and store the row compacted to the mask's set bits (k-th set bit -> slot k,
+// zeros behind).  Rows of intervals that cannot pair get a zero mask and zeros: k_pf_iloop has
+// items only for pairing closing pairs and never reads them.
+__global__ __launch_bounds__(256) void k_pf_ie(PfSetupDev T, long long nrows) {
+    const int n = T.v.n, rs = T.v.rs;
+    const int lane = threadIdx.x & 63, u2 = lane & 31;
+    const long long g = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (lane >> 5);
+    const long long per = (long long)(n + 1) * rs * PF_IEW;
+    const bool row_ok = g < nrows;
+    const long long gg = row_ok ? g : 0;
+    const int inner = gg >= per;
+    const long long rr = gg - (inner ? per : 0);
+    const int ix = (int)(rr / PF_IEW), u1 = (int)(rr - (long long)ix * PF_IEW);
+    const int w = ix / rs, p = ix - w * rs;
+    double wt = 0.0;
+    const bool on = row_ok && u2 < PF_IEW && p + w <= n &&
+                    (inner ? pf_ie_inner(T.v, w, p, u1, u2, wt) : pf_ie_outer(T.v, w, p, u1, u2, wt));
+    const unsigned long long bal = __ballot(on);
+    const uint32_t mk = (uint32_t)(bal >> (lane & 32));
+    if (!row_ok) return;
+    const int cnt = __builtin_popcount(mk), slot = __builtin_popcount(mk & ((1u << u2) - 1u));
+    double *row = (inner ? T.ieI : T.ieO) + rr * PF_IEW;
+    if (on) row[slot] = wt;
+    if (u2 >= cnt && u2 < PF_IEW) row[u2] = 0.0;
+    if (u2 == 0) (inner ? T.mI : T.mO)[rr] = mk;
+}
+
+struct PfDevPT {
+    const int8_t *pt;
+    int rs;
+    __device__ int operator()(int i, int j) const { return pt[(j - i) * rs + i]; }
+};
+
+// k_pf_iloop work items in the host builder's order, as k_items (ccj_kernels.hip): KI_SPLIT
+// workgroups per level each walk one run of its rows 256 at a time; pass 0 counts, pass 1 writes
+// at offs[t * KI_SPLIT + s] plus an exclusive scan of the row counts.
+__global__ __launch_bounds__(256) void k_pf_items(PfSetupDev T, long long *counts, const long long *__restrict__ offs,
+                                                  uint32_t *items, int pass) {
+    __shared__ int wsum[4];
+    const int bs = blockIdx.x, t = bs / KI_SPLIT, sp = bs - t * KI_SPLIT;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = T.v.n;
+    const PfDevPT pt{T.pt, T.v.rs};
+    int lo, hi;
+    ki_split_rows(pf_item_nrows(n, t), sp, lo, hi);
+    long long base = pass ? offs[bs] : 0;
+    for (int c0 = lo; c0 < hi; c0 += 256) {
+        const int x = c0 + tid;
+        uint32_t it0 = 0;
+        const int cnt = x < hi ? pf_item_row(pt, n, t, x, it0) : 0;
+        int inc = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += y;
+        }
+        if (lane == 63) wsum[wv] = inc;
+        __syncthreads();
+        int before = 0;
+        for (int v = 0; v < wv; ++v) before += wsum[v];
+        const int chunk_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (pass) {
+            const long long pos = base + before + inc - cnt;
+            for (int c = 0; c < cnt; ++c) items[pos + c] = it0 | (uint32_t)c;
+        }
+        base += chunk_total;
+        __syncthreads();  // wsum is rewritten by the next chunk
+    }
+    if (pass == 0 && tid == 0) counts[bs] = base;
+}
+
+}  // namespace
+
+extern "C" int ccjk_pf_setup_tables(const PfSetupDev *T, void *stream) {
+    const int n = T->v.n, plane = (n + 1) * T->v.rs;
+    hipLaunchKernelGGL(k_pf_seq_tables, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *T);
+    const long long nrows = 2LL * plane * PF_IEW;
+    hipLaunchKernelGGL(k_pf_ie, dim3((unsigned)((nrows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, *T, nrows);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_pf_items(const PfSetupDev *T, long long *counts, const long long *offs, uint32_t *items, int pass,
+                             void *stream) {
+    const int blocks = (T->v.n - 2) * KI_SPLIT;
+    if (blocks <= 0) return 0;
+    hipLaunchKernelGGL(k_pf_items, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *T, counts, offs, items, pass);
+    return (int)hipGetLastError();
+}

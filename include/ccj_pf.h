@@ -77,9 +77,47 @@ typedef struct ccj_pf_raw {
  * type 0 rows taken as INF, which every shipped set has).  device = HIP ordinal. */
 int ccj_pf_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, ccj_pf_ctx **out);
 void ccj_pf_destroy(ccj_pf_ctx *ctx);
-/* The device and host bytes ccj_pf_create allocates for a sequence of length n (its up-front size
- * check compares them with the device's free memory and the host's MemAvailable). */
+/* The device bytes ccj_pf_create allocates for a sequence of length n (its up-front size check
+ * compares them with the device's free memory), and the host bytes of the two window tables the
+ * host builder (CCJ_PF_HOST_SETUP=1) forms before it uploads them. */
 void ccj_pf_footprint(int n, unsigned long long *device_bytes, unsigned long long *host_bytes);
+
+/* One context, many sequences — the semantics of ccj_create_cap / ccj_rebind / ccj_reset (ccj.h,
+ * DESIGN.md §3.1) for the partition function.
+ *
+ * ccj_pf_create_cap allocates every buffer, event and pinned staging area for the largest demand
+ * over the lengths 1..capacity and builds the context's key tables (once: the interior-loop and
+ * stack weights by their arguments, host libm).  prob->seq (length <= capacity) is
+ * bound at once; NULL binds poly-A of the capacity.  ccj_pf_create(prob) is
+ * ccj_pf_create_cap(prob, strlen(prob->seq)): at n == capacity every offset and launch is that of
+ * a context created for n.
+ *
+ * ccj_pf_rebind binds another sequence of any length 1..capacity: it recomputes the row stride, the
+ * plane bases, the level descriptors and record bases, and rebuilds the per-sequence tables with
+ * kernels on the context's stream (pt, est, the weight windows and masks, the k_pf_iloop items;
+ * hp on the host, uploaded from pinned staging) with one wait (the item counts).  It allocates
+ * nothing.  ccj_pf_reset is ccj_pf_rebind for a sequence of the bound length (another length is
+ * CCJ_E_ARG).  A sequence longer than the capacity or with a character outside A/C/G/U/T is refused
+ * with CCJ_E_ARG before the context is touched: the previous binding stays usable.  After either
+ * call the context holds no fill (ccj_pf_W, ccj_pf_hashes, ccj_pf_sample ... return CCJ_E_STATE)
+ * until ccj_pf_fill.  The parameters, dangles, penalties, noGU and the ccj_pf_srand state belong to
+ * the context and stay.  A fill that ends in CCJ_E_PF_RANGE leaves the context able to take the
+ * next sequence.  CCJ_PF_HOST_SETUP=1 (read at each call) builds the tables on the host with one
+ * pow per entry instead, as before — the yardstick of the key tables. */
+int ccj_pf_create_cap(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int capacity, ccj_pf_ctx **out);
+int ccj_pf_rebind(ccj_pf_ctx *ctx, const char *seq);
+int ccj_pf_reset(ccj_pf_ctx *ctx, const char *seq);
+int ccj_pf_capacity(const ccj_pf_ctx *ctx);
+int ccj_pf_n(const ccj_pf_ctx *ctx); /* the bound length */
+/* The one-time key-table build of this context: host milliseconds and device bytes. */
+int ccj_pf_keytab_info(const ccj_pf_ctx *ctx, double *build_ms, unsigned long long *bytes);
+/* FNV-1a of the bound sequence's setup tables as they stand on the device (cap >= 8): pt, est, hp,
+ * the work items with their per-level firsts, then over the intervals whose pair can pair the
+ * compacted 29 x 29 weights of ieO and ieI and the 29 mask words of mO and mI. */
+int ccj_pf_setup_hashes(ccj_pf_ctx *ctx, uint64_t *out, int cap);
+/* No GPU: the hashes (est, ieO, ieI, mO, mI as above) of a problem's tables built with one pow per
+ * entry (direct5) and through the key tables and the gather functions the kernels share (keyed5). */
+int ccj_pf_setup_host_hashes(const ccj_problem *prob, const ccj_pf_raw *raw, uint64_t *direct5, uint64_t *keyed5);
 
 /* ccj_pf(): the whole fill on the GPU, then W on the host.  *energy = to_Energy(W[n], n)
  * (part_func.cc:148-150,173). */
@@ -126,7 +164,8 @@ int ccj_pf_timing(ccj_pf_ctx *ctx, float *fill_ms);
 int ccj_pf_set_timing(ccj_pf_ctx *ctx, int on);
 int ccj_pf_kernel_ms(ccj_pf_ctx *ctx, double *ms4);
 /* Algorithmic HBM bytes of one fill per kernel family (same order): the operands the
- * recurrences read and write, counted over this sequence's work items.  Host-side, no GPU work. */
+ * recurrences read and write, counted over this sequence's work items.  Host-side; the items and
+ * masks are fetched from the device on the first call after a setup. */
 int ccj_pf_work_model(ccj_pf_ctx *ctx, double *bytes4);
 
 #ifdef __cplusplus
