@@ -21,7 +21,7 @@ __all__ = [
     "num_cells", "comm_unique_id", "shard_blocks", "level_layout", "level_schedule", "LevelSchedule",
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
-    "pf_many", "pf_setup_host_hashes", "PF_SETUP_TABLES", "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
+    "pf_many", "PfLockstepBatch", "pf_level_plan", "PF_PLAN_KERNELS", "pf_setup_host_hashes", "PF_SETUP_TABLES", "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -258,6 +258,29 @@ def lib() -> ctypes.CDLL:
         L.ccj_pf_setup_hashes.restype = ip
         L.ccj_pf_setup_host_hashes.argtypes = [ctypes.POINTER(_Problem), cp, u64p, u64p]
         L.ccj_pf_setup_host_hashes.restype = ip
+    # (likewise the lockstep batch of the partition function)
+    if hasattr(L, "ccj_pf_batch_create"):
+        L.ccj_pf_batch_create.argtypes = [ctypes.POINTER(_Problem), cp, ip, ip, ip, ctypes.POINTER(vp)]
+        L.ccj_pf_batch_create.restype = ip
+        L.ccj_pf_batch_bind.argtypes = [vp, ctypes.POINTER(cp), ip]
+        L.ccj_pf_batch_bind.restype = ip
+        for fn in ("ccj_pf_batch_fill", "ccj_pf_batch_members", "ccj_pf_batch_count", "ccj_pf_batch_launches"):
+            getattr(L, fn).argtypes = [vp]
+            getattr(L, fn).restype = ip
+        L.ccj_pf_batch_result.argtypes = [vp, ip, dp]
+        L.ccj_pf_batch_result.restype = ip
+        L.ccj_pf_batch_member.argtypes = [vp, ip]
+        L.ccj_pf_batch_member.restype = vp
+        L.ccj_pf_batch_fill_ms.argtypes = [vp]
+        L.ccj_pf_batch_fill_ms.restype = ctypes.c_double
+        L.ccj_pf_batch_item_counts.argtypes = [vp, ip, ctypes.POINTER(ip)]
+        L.ccj_pf_batch_item_counts.restype = ip
+        L.ccj_pf_batch_last_error.argtypes = [vp]
+        L.ccj_pf_batch_last_error.restype = cp
+        L.ccj_pf_batch_destroy.argtypes = [vp]
+        L.ccj_pf_batch_destroy.restype = None
+        L.ccj_pf_level_plan_items.argtypes = [ctypes.POINTER(ip), ctypes.POINTER(ip), ip, ip, ctypes.POINTER(ip)]
+        L.ccj_pf_level_plan_items.restype = ip
     L.ccj_pf_fill.argtypes = [vp, dp]
     L.ccj_pf_fill.restype = ip
     L.ccj_pf_W.argtypes = [vp, dp]
@@ -969,15 +992,36 @@ def pf_setup_host_hashes(seq: str, dangle: int = 2, params: str | bytes = "Dirks
     return ({k: "%016x" % v for k, v in zip(names, a)}, {k: "%016x" % v for k, v in zip(names, b)})
 
 
+def _pf_many_lockstep(seqs, k, dangle, params, noGU, device, capacity) -> list:
+    runs = plan_lockstep([len(s) for s in seqs], k)
+    cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
+    out: list = [None] * len(seqs)
+    batch = PfLockstepBatch(cap, min(max(1, int(k)), len(seqs)), dangle, params=params, noGU=noGU, device=device)
+    try:
+        for run in runs:
+            batch.bind([seqs[x] for x in run])
+            batch.fill()
+            for x, pf in zip(run, batch.members):
+                out[x] = (seqs[x], None, pf.refused) if pf.refused is not None else (seqs[x], pf.energy, pf.W()[-1])
+    finally:
+        batch.close()
+    return out
+
+
 def pf_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False, device: int = 0,
-            capacity: Optional[int] = None) -> list:
+            capacity: Optional[int] = None, lockstep: int = 0) -> list:
     """The partition function of every sequence through one capacity context (capacity: the longest
     sequence by default), rebind + fill each.  Returns one record per sequence, in input order:
     (seq, energy, W(n)).  A fold that fails (CCJ_E_PF_RANGE: the exactness guard) is recorded as
-    (seq, None, CCJError) and does not disturb the others."""
+    (seq, None, CCJError) and does not disturb the others.
+    lockstep=K > 0: instead, sort by length, cut into runs of K neighbours (plan_lockstep) and fill each
+    run as one PfLockstepBatch, which pays every level's launches once per run; the same records, in
+    input order."""
     seqs = list(seqs)
     if not seqs:
         return []
+    if lockstep and int(lockstep) > 0:
+        return _pf_many_lockstep(seqs, int(lockstep), dangle, params, noGU, device, capacity)
     cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
     out: list = []
     pf = W_final_pf(seqs[0], dangle=dangle, params=params, noGU=noGU, device=device, capacity=cap)
@@ -1163,8 +1207,124 @@ class W_final_pf:
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().ccj_pf_destroy(self._h)
+            lib().ccj_pf_destroy(self._h)  # ignores a lockstep batch's member: PfLockstepBatch.close frees it
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PF_PLAN_KERNELS = ("k_pf_iloop", "k_pf_level", "k_pf_ppush", "k_pf_diag")
+
+
+def pf_level_plan(lengths, t: int, item_counts=None) -> dict:
+    """The launches a partition-function fill enqueues with level t for members of these lengths (no
+    GPU needed; include/ccj_pf.h ccj_pf_level_plan): k_pf_iloop(t+2), k_pf_level(t), k_pf_ppush(t),
+    k_pf_diag(t+3); t = -3, -2, -1 are the launches ahead of level 0.  Returns {kernel: (grid,
+    members)}: grid = the one launch's (x, y, z), members = the grid each member would launch alone;
+    (0, 0, 0) = no launch.  item_counts: each member's k_pf_iloop items of level t+2
+    (PfLockstepBatch.item_counts); without them that family is (-1, -1, -1) wherever the level exists."""
+    lengths = [int(x) for x in lengths]
+    cnt = len(lengths)
+    n = (ctypes.c_int * max(cnt, 1))(*lengths)
+    items = None
+    if item_counts is not None:
+        if len(item_counts) != cnt:
+            raise CCJError(CCJ_E_ARG, "pf_level_plan: one item count per member")
+        items = (ctypes.c_int * max(cnt, 1))(*[int(x) for x in item_counts])
+    out = (ctypes.c_int * (12 + 12 * max(cnt, 1)))()
+    rc = lib().ccj_pf_level_plan_items(n, items, cnt, int(t), out)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "bad plan arguments")
+    g = [tuple(out[3 * q: 3 * q + 3]) for q in range(4 + 4 * cnt)]
+    return {name: (g[f], tuple(g[4 + 4 * k + f] for k in range(cnt))) for f, name in enumerate(PF_PLAN_KERNELS)}
+
+
+class PfLockstepBatch:
+    """`members` capacity contexts of the partition function filled in lockstep (include/ccj_pf.h
+    ccj_pf_batch): bind(seqs) gives member k the k-th sequence, fill() runs every bound member's fill
+    in one set of level launches, then W and the energy per member.  Afterwards each bound member (a
+    W_final_pf over the borrowed context) has `energy` set, or `refused` = its CCJError where the
+    fold ended in CCJ_E_PF_RANGE (the other members are untouched); W(), hashes(), get2, get4,
+    srand and sample work on it, its own rebind / reset / ccj_pf raise CCJ_E_STATE."""
+
+    def __init__(self, capacity: int, members: int, dangle: int = 2, params: str | bytes = "DirksPierce09",
+                 noGU: bool = False, device: int = 0, pen=None):
+        L = lib()
+        prob, self._keep = _pf_problem(None, dangle, params, noGU, pen)
+        self._raw = load_pfraw(params)
+        h = ctypes.c_void_p()
+        rc = L.ccj_pf_batch_create(ctypes.byref(prob), self._raw, device, int(capacity), int(members), ctypes.byref(h))
+        if rc != CCJ_OK:
+            raise CCJError(rc, L.ccj_pf_batch_last_error(None).decode())
+        self._h = h
+        self.capacity = int(capacity)
+        self.dangle = dangle
+        self._all = []
+        for k in range(int(members)):
+            pf = W_final_pf.__new__(W_final_pf)
+            pf._h = ctypes.c_void_p(L.ccj_pf_batch_member(h, k))
+            pf._keep, pf._raw = self._keep, self._raw
+            pf.MFE_structure, pf.MFE_energy, pf.num_samples, pf.PSplot, pf.structures = "", 0.0, 0, False, {}
+            pf._bound("")
+            pf.refused = None
+            self._all.append(pf)
+        self.count = 0
+
+    @property
+    def members(self) -> list:
+        """The bound members, in the order of the last bind()."""
+        return self._all[: self.count]
+
+    @property
+    def size(self) -> int:
+        return len(self._all)
+
+    def _check(self, rc: int):
+        if rc != CCJ_OK:
+            raise CCJError(rc, lib().ccj_pf_batch_last_error(self._h).decode())
+
+    def bind(self, seqs) -> None:
+        seqs = [str(s) for s in seqs]
+        arr = (ctypes.c_char_p * max(len(seqs), 1))(*[s.encode() for s in seqs])
+        self._check(lib().ccj_pf_batch_bind(self._h, arr, len(seqs)))
+        self.count = len(seqs)
+        for pf, s in zip(self._all, seqs):
+            pf._bound(s)
+            pf.refused = None
+
+    def fill(self) -> None:
+        L = lib()
+        self._check(L.ccj_pf_batch_fill(self._h))
+        e = ctypes.c_double()
+        for k, pf in enumerate(self.members):
+            rc = L.ccj_pf_batch_result(self._h, k, ctypes.byref(e))
+            pf.energy, pf.refused = (e.value, None) if rc == CCJ_OK else (None, CCJError(rc, L.ccj_pf_last_message(pf._h).decode()))
+            if rc not in (CCJ_OK, CCJ_E_PF_RANGE):
+                raise pf.refused
+
+    def item_counts(self, t: int) -> list:
+        """Each bound member's k_pf_iloop work items of level t (0 where it has no such level)."""
+        out = (ctypes.c_int * max(self.count, 1))()
+        self._check(lib().ccj_pf_batch_item_counts(self._h, int(t), out))
+        return list(out[: self.count])
+
+    def fill_ms(self) -> float:
+        return lib().ccj_pf_batch_fill_ms(self._h)
+
+    def launches(self) -> int:
+        """Kernel launches the last fill() enqueued."""
+        return lib().ccj_pf_batch_launches(self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            for pf in self._all:
+                pf._h = None
+            lib().ccj_pf_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
 
     def __del__(self):
         try:

@@ -9,6 +9,8 @@
 // A context serves many sequences (ccj_pf_create_cap / ccj_pf_rebind / ccj_pf_reset): the pow()
 // values are tabulated once per context by their arguments (ccj_pf_setup.h) and the per-sequence
 // tables are gathered from them by kernels; CCJ_PF_HOST_SETUP=1 keeps the direct host builder.
+// A lockstep batch (ccj_pf_batch_*) fills K such contexts with one event graph: one launch per level
+// or span for all of them (the k_pf_*_many entries of ccj_pf.hip).
 //
 // Everything here is evaluated as written, without floating-point contraction, with the host
 // libm — the same exp/log/pow/sin the reference links — so the device only ever multiplies and
@@ -165,6 +167,10 @@ constexpr int kNExp = 22;
 }  // namespace
 
 struct ccj_pf_ctx {
+    // a lockstep batch's member (ccj_pf_batch): st is the batch's stream and the model's device tables
+    // (d_E, d_pair, d_rtype, d_mlb, d_cpp, d_pup, d_ietab, d_esttab) are the batch's, all borrowed; it
+    // has no streams, events or timing of its own, and only the batch binds, fills and frees it
+    ccj_pf_batch *batch = nullptr;
     int n = 0, rs = 0, dangles = 2, device = 0;
     int cap = 0;     // capacity N: every buffer holds any length 1..N (ccj_pf_create_cap)
     int noGU = 0;
@@ -205,6 +211,7 @@ struct ccj_pf_ctx {
     double *d_R = nullptr;                  // k_pf_iloop's sums of one level, 3 planes of max C_t
     uint32_t *d_items = nullptr, *d_mO = nullptr, *d_mI = nullptr;
     std::vector<long long> ifirst;          // k_pf_iloop items of level t: [ifirst[t], ifirst[t+1])
+    bool setup_pending = false;             // between setup_seq_a and setup_seq_b
     std::vector<uint32_t> h_items, h_mO, h_mI;  // host copies (ccj_pf_work_model)
     PfLvl *d_ld = nullptr;
     hipStream_t st = nullptr;     // levels (k_pf_level), the memsets, the result copies
@@ -235,6 +242,22 @@ struct ccj_pf_ctx {
     size_t plane() const { return (size_t)(n + 1) * rs; }
     double g2(int m, int i, int j) const { return i > j ? 0.0 : h2d[(size_t)m * plane() + (size_t)(j - i) * rs + i]; }
     int ptype(int i, int j) const { return pair[S[i]][S[j]]; }
+};
+
+// A lockstep batch: `model` holds what the members share (the model's host and device tables, the
+// main stream) and the one fill graph (its streams and events, sized for the capacity); it is never
+// bound to a sequence.  mem[k] are capacity contexts that borrow from it (ccj_pf_ctx::batch).
+struct ccj_pf_batch {
+    ccj_pf_ctx model;
+    std::vector<ccj_pf_ctx *> mem;
+    int count = 0, nmax = 0;      // bound members; the longest of them
+    std::vector<int> n;           // their lengths
+    std::vector<int> rc;          // each member's outcome of the last fill
+    PfDev *d_D = nullptr, *h_D = nullptr;          // the bound members' PfDev (device; pinned staging)
+    long long *d_if = nullptr, *h_if = nullptr;    // k_pf_iloop_many's table: row k = member k's ifirst[]
+    int stride = 0;                                // its row length (capacity + 1)
+    int launches = 0;
+    std::string msg;
 };
 
 // The allocations of ccj_pf_create for a sequence of length n, in bytes: device (every hipMalloc
@@ -367,10 +390,13 @@ void run_threads(int total, int nthr, const std::function<void(int, int)> &f) {
 }
 
 void free_dev(ccj_pf_ctx *c) {
-    void *ptrs[] = {c->d_E, c->d_S, c->d_S1, c->d_pt, c->d_pair, c->d_rtype, c->d_hp, c->d_est, c->d_ieO, c->d_ieI,
-                    c->d_mlb, c->d_cpp, c->d_pup, c->d_2d, c->d_Pacc, c->d_Pabs, c->d_d4, c->d_cx, c->d_pmx,
-                    c->d_prec, c->d_R, c->d_items, c->d_mO, c->d_mI, c->d_ld, c->d_ietab, c->d_esttab, c->d_icount,
+    void *model[] = {c->d_E, c->d_pair, c->d_rtype, c->d_mlb, c->d_cpp, c->d_pup, c->d_ietab, c->d_esttab};
+    void *ptrs[] = {c->d_S, c->d_S1, c->d_pt, c->d_hp, c->d_est, c->d_ieO, c->d_ieI, c->d_2d, c->d_Pacc, c->d_Pabs,
+                    c->d_d4, c->d_cx, c->d_pmx, c->d_prec, c->d_R, c->d_items, c->d_mO, c->d_mI, c->d_ld, c->d_icount,
                     c->d_ioff};
+    if (!c->batch)
+        for (void *p : model)
+            if (p) hipFree(p);
     for (void *p : ptrs)
         if (p) hipFree(p);
     void *pinned[] = {c->h_S, c->h_hp, c->h_lv, c->h_icount, c->h_ioff};
@@ -388,7 +414,7 @@ void free_dev(ccj_pf_ctx *c) {
     if (c->ev_start) hipEventDestroy(c->ev_start);
     if (c->st_il) hipStreamDestroy(c->st_il);
     if (c->st_d) hipStreamDestroy(c->st_d);
-    if (c->st) hipStreamDestroy(c->st);
+    if (c->st && !c->batch) hipStreamDestroy(c->st);
 }
 
 // Algorithmic bytes of one fill per kernel family (ccj_pf_work_model): the operands each kernel's
@@ -815,24 +841,33 @@ bool make_layout(int n, PfLayout &Y) {
 }
 const char *const kPpushMsg = "n too large: the PK rows of 8 levels exceed 4 GB (k_pf_ppush offsets)";
 
-// Allocation for a capacity N: every buffer, event and pinned staging area at its maximum over the
-// lengths 1..N.  Each size grows with the length, so the layout of N gives the maxima.
-int alloc_cap(ccj_pf_ctx *c, int N, int device, const PfLayout &Y) {
+// The streams and events of one fill graph for lengths up to N (a context's, or a batch's).
+struct PfGraph {
+    hipStream_t *st, *st_il, *st_d;
+    std::vector<hipEvent_t> *ev_lev, *ev_il, *ev_dg;
+    hipEvent_t *ev_start, *e0, *e1;
+};
+hipError_t make_graph(const PfGraph &g, int N) {
+    hipError_t e;
+    for (hipStream_t *s : {g.st, g.st_il, g.st_d})
+        if ((e = hipStreamCreateWithFlags(s, hipStreamNonBlocking)) != hipSuccess) return e;
+    if ((e = hipEventCreateWithFlags(g.ev_start, hipEventDisableTiming)) != hipSuccess) return e;
+    for (auto *v : {g.ev_lev, g.ev_il, g.ev_dg}) {
+        v->assign(N + 1, nullptr);
+        for (hipEvent_t &x : *v)
+            if ((e = hipEventCreateWithFlags(&x, hipEventDisableTiming)) != hipSuccess) return e;
+    }
+    if ((e = hipEventCreate(g.e0)) != hipSuccess) return e;
+    return hipEventCreate(g.e1);
+}
+
+// Once per context, or once per lockstep batch: the fill graph and the model's device tables
+// (Boltzmann tables, powers, key tables) for lengths up to N.
+int alloc_model(ccj_pf_ctx *c, int N, int device) {
     c->cap = N;
     c->device = device;
-    const size_t plane = (size_t)(N + 1) * (N + 2);
-    constexpr int W2 = PF_IEW * PF_IEW;
     PFCHK(c, hipSetDevice(device));
-    PFCHK(c, hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    PFCHK(c, hipStreamCreateWithFlags(&c->st_il, hipStreamNonBlocking));
-    PFCHK(c, hipStreamCreateWithFlags(&c->st_d, hipStreamNonBlocking));
-    PFCHK(c, hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming));
-    for (auto *v : {&c->ev_lev, &c->ev_il, &c->ev_dg}) {
-        v->assign(N + 1, nullptr);
-        for (hipEvent_t &e : *v) PFCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    PFCHK(c, hipEventCreate(&c->e0));
-    PFCHK(c, hipEventCreate(&c->e1));
+    PFCHK(c, make_graph(PfGraph{&c->st, &c->st_il, &c->st_d, &c->ev_lev, &c->ev_il, &c->ev_dg, &c->ev_start, &c->e0, &c->e1}, N));
     auto up = [&](void **d, const void *h, size_t bytes) -> hipError_t {
         hipError_t e = hipMalloc(d, bytes ? bytes : 8);
         if (e != hipSuccess) return e;
@@ -843,20 +878,46 @@ int alloc_cap(ccj_pf_ctx *c, int N, int device, const PfLayout &Y) {
         rt8[x] = (int8_t)c->rtype[x];
         for (int y = 0; y < 8; ++y) pair8[x * 8 + y] = (int8_t)c->pair[x][y];
     }
-    // once per context: the model's tables
     PFCHK(c, up((void **)&c->d_E, &c->E, sizeof(PfExp)));
     PFCHK(c, up((void **)&c->d_pair, pair8, 64));
     PFCHK(c, up((void **)&c->d_rtype, rt8, 8));
     PFCHK(c, up((void **)&c->d_mlb, c->mlb.data(), c->mlb.size() * sizeof(double)));
     PFCHK(c, up((void **)&c->d_cpp, c->cpp.data(), c->cpp.size() * sizeof(double)));
     PFCHK(c, up((void **)&c->d_pup, c->pup.data(), c->pup.size() * sizeof(double)));
-    {
-        std::vector<double> ietab;
-        const auto t0 = std::chrono::steady_clock::now();
-        build_keytab(*c, N, ietab, c->esttab);
-        c->keytab_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        PFCHK(c, up((void **)&c->d_ietab, ietab.data(), ietab.size() * sizeof(double)));
-        PFCHK(c, up((void **)&c->d_esttab, c->esttab, sizeof c->esttab));
+    std::vector<double> ietab;
+    const auto t0 = std::chrono::steady_clock::now();
+    build_keytab(*c, N, ietab, c->esttab);
+    c->keytab_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    PFCHK(c, up((void **)&c->d_ietab, ietab.data(), ietab.size() * sizeof(double)));
+    PFCHK(c, up((void **)&c->d_esttab, c->esttab, sizeof c->esttab));
+    return CCJ_OK;
+}
+
+// Allocation for a capacity N: every buffer, event and pinned staging area at its maximum over the
+// lengths 1..N.  Each size grows with the length, so the layout of N gives the maxima.
+// share: a batch's model context, which owns the model's device tables and the stream: c (a member,
+// c->batch set) borrows them and gets no fill graph of its own.
+int alloc_cap(ccj_pf_ctx *c, int N, int device, const PfLayout &Y, const ccj_pf_ctx *share = nullptr) {
+    const size_t plane = (size_t)(N + 1) * (N + 2);
+    constexpr int W2 = PF_IEW * PF_IEW;
+    if (share) {
+        c->cap = N;
+        c->device = device;
+        c->st = share->st;
+        c->d_E = share->d_E;
+        c->d_pair = share->d_pair;
+        c->d_rtype = share->d_rtype;
+        c->d_mlb = share->d_mlb;
+        c->d_cpp = share->d_cpp;
+        c->d_pup = share->d_pup;
+        c->d_ietab = share->d_ietab;
+        c->d_esttab = share->d_esttab;
+        memcpy(c->esttab, share->esttab, sizeof c->esttab);
+        c->keytab_ms = share->keytab_ms;
+        PFCHK(c, hipSetDevice(device));
+    } else {
+        const int rc = alloc_model(c, N, device);
+        if (rc != CCJ_OK) return rc;
     }
     // per sequence
     PFCHK(c, hipMalloc((void **)&c->d_S, (size_t)(N + 2) * sizeof(short)));
@@ -957,11 +1018,26 @@ bool host_setup() {
     return e && atoi(e) != 0;
 }
 
+PfSetupDev setup_dev(const ccj_pf_ctx *c) {
+    PfSetupDev T;
+    T.v = PfSeqView{c->n, c->rs, c->d_S, c->d_pair, c->d_rtype, c->d_ietab, c->d_esttab};
+    T.pt = c->d_pt;
+    T.est = c->d_est;
+    T.ieO = c->d_ieO;
+    T.ieI = c->d_ieI;
+    T.mO = c->d_mO;
+    T.mI = c->d_mI;
+    return T;
+}
+
 // The per-sequence state of the bound sequence, on the context's stream: S / S1 and hp (host,
 // through pinned staging), the copies zeroed, then pt, est, ieO / ieI, mO / mI and the work items
 // by the setup kernels (ccj_pf.hip).  One wait: the item counts, whose prefix the host forms.
 // CCJ_PF_HOST_SETUP=1: the tables of host_tables() instead, uploaded with blocking copies.
-int setup_seq(ccj_pf_ctx *c) {
+// In two halves around that wait, so that a lockstep batch waits once for all its members:
+// setup_seq_a enqueues everything up to the copy of the item counts, setup_seq_b (after the
+// stream has been synchronized) forms their prefix and enqueues the items pass.
+int setup_seq_a(ccj_pf_ctx *c) {
     const int n = c->n, N2 = c->cap + 2;
     const size_t plane = c->plane();
     constexpr int W2 = PF_IEW * PF_IEW;
@@ -979,6 +1055,7 @@ int setup_seq(ccj_pf_ctx *c) {
     PFCHK(c, hipMemsetAsync(c->d_cx, 0, (size_t)std::max(c->offx, 1LL) * sizeof(int), c->st));
     PFCHK(c, hipMemsetAsync(c->d_pmx, 0, (size_t)std::max(c->offm, 1LL) * sizeof(int), c->st));
     c->ifirst.assign(std::max(n - 1, 2), 0);
+    c->setup_pending = false;
     if (host_setup()) {
         build_hp(*c, c->h_hp);
         PFCHK(c, hipMemcpyAsync(c->d_hp, c->h_hp, plane * sizeof(double), hipMemcpyHostToDevice, c->st));
@@ -997,14 +1074,7 @@ int setup_seq(ccj_pf_ctx *c) {
         c->ifirst = T.ifirst;
         return CCJ_OK;
     }
-    PfSetupDev T;
-    T.v = PfSeqView{n, c->rs, c->d_S, c->d_pair, c->d_rtype, c->d_ietab, c->d_esttab};
-    T.pt = c->d_pt;
-    T.est = c->d_est;
-    T.ieO = c->d_ieO;
-    T.ieI = c->d_ieI;
-    T.mO = c->d_mO;
-    T.mI = c->d_mI;
+    const PfSetupDev T = setup_dev(c);
     PFCHK(c, (hipError_t)ccjk_pf_setup_tables(&T, c->st));
     PFCHK(c, hipMemsetAsync(c->d_ieO + W2 * plane, 0, PF_ILW * sizeof(double), c->st));
     PFCHK(c, hipMemsetAsync(c->d_ieI + W2 * plane, 0, PF_ILW * sizeof(double), c->st));
@@ -1017,7 +1087,16 @@ int setup_seq(ccj_pf_ctx *c) {
     // hp: the special-hairpin strstr cases stay on the host; built while the kernels run
     build_hp(*c, c->h_hp);
     PFCHK(c, hipMemcpyAsync(c->d_hp, c->h_hp, plane * sizeof(double), hipMemcpyHostToDevice, c->st));
-    PFCHK(c, hipStreamSynchronize(c->st));  // the one wait of a reset: the item counts
+    c->setup_pending = true;
+    return CCJ_OK;
+}
+
+int setup_seq_b(ccj_pf_ctx *c) {
+    if (!c->setup_pending) return CCJ_OK;  // the host builder left nothing to do
+    c->setup_pending = false;
+    const int n = c->n, nl = std::max(n - 2, 0);
+    const size_t nsp = (size_t)nl * KI_SPLIT;
+    const PfSetupDev T = setup_dev(c);
     long long o = 0;
     for (int t = 0; t < nl; ++t) {
         c->ifirst[t] = o;
@@ -1033,6 +1112,13 @@ int setup_seq(ccj_pf_ctx *c) {
         PFCHK(c, (hipError_t)ccjk_pf_items(&T, nullptr, c->d_ioff, c->d_items, 1, c->st));
     }
     return CCJ_OK;
+}
+
+int setup_seq(ccj_pf_ctx *c) {
+    int rc = setup_seq_a(c);
+    if (rc != CCJ_OK || !c->setup_pending) return rc;
+    PFCHK(c, hipStreamSynchronize(c->st));  // the one wait of a reset: the item counts
+    return setup_seq_b(c);
 }
 
 // Rebind an open context to seq (any length up to the capacity; the bound length = a reset).
@@ -1095,6 +1181,43 @@ int create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int 
     set_seq_host(c, seq.c_str());
     rc = bind_len(c, Y);
     return rc != CCJ_OK ? rc : setup_seq(c);
+}
+
+// The host's end of a fill, over the copies of the 2-D planes (c->h2d) and of Pabs: the exactness
+// check, W and the energy.  CCJ_E_PF_RANGE leaves the context without a fill.
+int finish_fill(ccj_pf_ctx *c, const unsigned long long *pabs) {
+    const int n = c->n;
+    // the exact int64 P sums equal the reference's serial double sums only while every partial sum
+    // is an exactly representable integer: guaranteed by sum |term| < 2^53 (part_func.cc:383-393)
+    // CCJ_PF_RANGE_LOG2 lowers the 2^53 bound (tests only: reaches this exit with short sequences)
+    unsigned long long range_lim = 1ull << 53;
+    if (const char *e = getenv("CCJ_PF_RANGE_LOG2")) {
+        const int l2 = atoi(e);
+        if (l2 >= 1 && l2 <= 53) range_lim = 1ull << l2;
+    }
+    for (int w = 0; w < n; ++w)
+        for (int p = 1; p + w <= n; ++p)
+            if (pabs[(size_t)w * c->rs + p] >= range_lim) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "P(%d,%d): sum of |terms| >= 2^53, the reference's double sum may round", p, p + w);
+                return pf_err(c, CCJ_E_PF_RANGE, msg);
+            }
+    // W (part_func.cc:163-172)
+    c->W.assign(n + 1, 1.0);  // W.resize(n+1, scale[1])
+    for (int j = TURN + 1; j <= n; ++j) {
+        double s = 0;
+        s += c->W[j - 1] * 1.0;
+        for (int k = 1; k <= j - TURN - 1; ++k) {
+            const double acc = (k > 1) ? c->W[k - 1] : 1;
+            s += acc * c->g2(CCJ_PF_V, k, j) * ext_pf(*c, k, j);
+            s += acc * c->g2(CCJ_PF_P, k, j) * c->E.PS;
+        }
+        c->W[j] = s;
+    }
+    // to_Energy (part_func.cc:148-150)
+    c->energy = (-log(c->W[n]) - n * log(c->E.pf_scale)) * c->E.kT / 1000.0;
+    c->filled = true;
+    return CCJ_OK;
 }
 
 int fill_impl(ccj_pf_ctx *c) {
@@ -1173,44 +1296,233 @@ int fill_impl(ccj_pf_ctx *c) {
     std::vector<unsigned long long> pabs(plane, 0);
     PFCHK(c, hipMemcpyAsync(pabs.data(), c->d_Pabs, plane * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
     PFCHK(c, hipStreamSynchronize(c->st));
-    // the exact int64 P sums equal the reference's serial double sums only while every partial sum
-    // is an exactly representable integer: guaranteed by sum |term| < 2^53 (part_func.cc:383-393)
-    // CCJ_PF_RANGE_LOG2 lowers the 2^53 bound (tests only: reaches this exit with short sequences)
-    unsigned long long range_lim = 1ull << 53;
-    if (const char *e = getenv("CCJ_PF_RANGE_LOG2")) {
-        const int l2 = atoi(e);
-        if (l2 >= 1 && l2 <= 53) range_lim = 1ull << l2;
-    }
-    for (int w = 0; w < n; ++w)
-        for (int p = 1; p + w <= n; ++p)
-            if (pabs[(size_t)w * c->rs + p] >= range_lim) {
-                char msg[160];
-                snprintf(msg, sizeof msg, "P(%d,%d): sum of |terms| >= 2^53, the reference's double sum may round", p, p + w);
-                return pf_err(c, CCJ_E_PF_RANGE, msg);
-            }
-    PFCHK(c, hipEventElapsedTime(&c->fill_ms, c->e0, c->e1));
-    for (double &k : c->kms) k = 0;
+    float fill_ms = 0;
+    double kms[4] = {0, 0, 0, 0};
+    PFCHK(c, hipEventElapsedTime(&fill_ms, c->e0, c->e1));
     for (size_t q = 0; q < c->tfam.size(); ++q) {
         float ms = 0;
         PFCHK(c, hipEventElapsedTime(&ms, c->tev[2 * q], c->tev[2 * q + 1]));
-        c->kms[c->tfam[q]] += ms;
+        kms[c->tfam[q]] += ms;
     }
+    const int rc = finish_fill(c, pabs.data());
+    if (rc != CCJ_OK) return rc;
+    c->fill_ms = fill_ms;
+    memcpy(c->kms, kms, sizeof kms);
+    return CCJ_OK;
+}
 
-    // W (part_func.cc:163-172)
-    c->W.assign(n + 1, 1.0);  // W.resize(n+1, scale[1])
-    for (int j = TURN + 1; j <= n; ++j) {
-        double s = 0;
-        s += c->W[j - 1] * 1.0;
-        for (int k = 1; k <= j - TURN - 1; ++k) {
-            const double acc = (k > 1) ? c->W[k - 1] : 1;
-            s += acc * c->g2(CCJ_PF_V, k, j) * ext_pf(*c, k, j);
-            s += acc * c->g2(CCJ_PF_P, k, j) * c->E.PS;
-        }
-        c->W[j] = s;
+// ---------------------------------------------------------------------------------------------
+// Lockstep batch (include/ccj_pf.h): K capacity contexts filled by one event graph.
+// ---------------------------------------------------------------------------------------------
+thread_local std::string g_batch_create_msg;
+
+int batch_err(ccj_pf_batch *b, int code, const std::string &what, hipError_t e = hipSuccess) {
+    b->msg = e == hipSuccess ? what : what + ": " + hipGetErrorString(e);
+    return code;
+}
+#define PBCHK(b, x)                                                      \
+    do {                                                                 \
+        const hipError_t e_ = (x);                                       \
+        if (e_ != hipSuccess) return batch_err((b), CCJ_E_HIP, #x, e_);  \
+    } while (0)
+
+void batch_free(ccj_pf_batch *b) {
+    hipSetDevice(b->model.device);
+    for (ccj_pf_ctx *c : b->mem) {
+        free_dev(c);
+        delete c;
     }
-    // to_Energy (part_func.cc:148-150)
-    c->energy = (-log(c->W[n]) - n * log(c->E.pf_scale)) * c->E.kT / 1000.0;
-    c->filled = true;
+    b->mem.clear();
+    if (b->d_D) hipFree(b->d_D);
+    if (b->d_if) hipFree(b->d_if);
+    if (b->h_D) hipHostFree(b->h_D);
+    if (b->h_if) hipHostFree(b->h_if);
+    free_dev(&b->model);
+}
+
+int batch_create_impl(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int N, int K, ccj_pf_batch *b) {
+    if (N > 1023) return batch_err(b, CCJ_E_ARG, "capacity above 1023");
+    ccj_pf_ctx *m = &b->model;
+    int rc = init_model(prob, raw, m);
+    if (rc != CCJ_OK) return batch_err(b, rc, m->msg);
+    PfLayout YN;
+    if (!make_layout(N, YN)) return batch_err(b, CCJ_E_ARG, kPpushMsg);
+    {   // the members' allocations and the shared tables against the free memory, before any of them
+        unsigned long long dev_b = 0;
+        ccj_pf_footprint(N, &dev_b, nullptr);
+        const double need = (double)K * (double)dev_b + (double)PF_KEYS * sizeof(double) + sizeof(PfExp);
+        size_t dfree = 0, dtotal = 0;
+        const char *lim = getenv("CCJ_PF_DEVMEM_LIMIT");
+        if (lim && *lim) dfree = (size_t)strtoull(lim, nullptr, 10);
+        else if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&dfree, &dtotal) != hipSuccess) dfree = SIZE_MAX;
+        if (need > (double)dfree) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "%d members of capacity %d need ~%.1f GB of device memory, %.1f GB free", K, N, need / 1e9,
+                     dfree / 1e9);
+            return batch_err(b, CCJ_E_OOM, msg);
+        }
+    }
+    build_powers(m, N);
+    rc = alloc_model(m, N, device);
+    if (rc != CCJ_OK) return batch_err(b, rc, m->msg);
+    const std::string polyA((size_t)N, 'A');
+    PfLayout Y1;
+    make_layout(1, Y1);
+    for (int k = 0; k < K; ++k) {
+        ccj_pf_ctx *c = new ccj_pf_ctx();
+        b->mem.push_back(c);
+        c->batch = b;
+        initstate_r(1, c->rnd_state, sizeof c->rnd_state, &c->rnd);
+        // the model on the host: a member evaluates hairpins, W and samples with its own copy
+        c->dangles = m->dangles;
+        c->noGU = m->noGU;
+        c->prm = m->prm;
+        c->pen = m->pen;
+        memcpy(c->pair, m->pair, sizeof c->pair);
+        memcpy(c->rtype, m->rtype, sizeof c->rtype);
+        c->E = m->E;
+        c->mlb = m->mlb;
+        c->cpp = m->cpp;
+        c->pup = m->pup;
+        rc = alloc_cap(c, N, device, YN, m);
+        if (rc != CCJ_OK) return batch_err(b, rc, c->msg);
+        // until the first bind a member stands at length 1, without a fill
+        set_seq_host(c, "A");
+        rc = bind_len(c, Y1);
+        if (rc == CCJ_OK) rc = setup_seq(c);
+        if (rc != CCJ_OK) return batch_err(b, rc, c->msg);
+    }
+    b->stride = N + 1;
+    PBCHK(b, hipMalloc((void **)&b->d_D, (size_t)K * sizeof(PfDev)));
+    PBCHK(b, hipMalloc((void **)&b->d_if, (size_t)K * b->stride * sizeof(long long)));
+    PBCHK(b, hipHostMalloc((void **)&b->h_D, (size_t)K * sizeof(PfDev)));
+    PBCHK(b, hipHostMalloc((void **)&b->h_if, (size_t)K * b->stride * sizeof(long long)));
+    PBCHK(b, hipStreamSynchronize(m->st));
+    return CCJ_OK;
+}
+
+int batch_bind_impl(ccj_pf_batch *b, const char *const *seqs, int count) {
+    const int K = (int)b->mem.size(), N = b->model.cap;
+    if (!seqs || count < 1 || count > K) return batch_err(b, CCJ_E_ARG, "ccj_pf_batch_bind: count must be 1..members");
+    // every argument before any member is touched
+    std::vector<PfLayout> Y((size_t)count);
+    for (int k = 0; k < count; ++k) {
+        const int rc = check_seq(&b->model, seqs[k], N);
+        if (rc != CCJ_OK) return batch_err(b, rc, "member " + std::to_string(k) + ": " + b->model.msg);
+        if (!make_layout((int)strlen(seqs[k]), Y[k])) return batch_err(b, CCJ_E_ARG, kPpushMsg);
+    }
+    hipStream_t st = b->model.st;
+    PBCHK(b, hipSetDevice(b->model.device));
+    b->count = 0;  // a failure below leaves the batch unbound
+    for (ccj_pf_ctx *c : b->mem) c->filled = false;
+    b->rc.assign(K, CCJ_E_STATE);
+    for (int k = 0; k < count; ++k) {
+        ccj_pf_ctx *c = b->mem[k];
+        set_seq_host(c, seqs[k]);
+        int rc = bind_len(c, Y[k]);
+        if (rc == CCJ_OK) rc = setup_seq_a(c);
+        if (rc != CCJ_OK) return batch_err(b, rc, c->msg);
+    }
+    PBCHK(b, hipStreamSynchronize(st));  // the one wait of a bind: every member's item counts
+    memset(b->h_if, 0, (size_t)K * b->stride * sizeof(long long));
+    b->n.assign(count, 0);
+    b->nmax = 0;
+    for (int k = 0; k < count; ++k) {
+        ccj_pf_ctx *c = b->mem[k];
+        const int rc = setup_seq_b(c);
+        if (rc != CCJ_OK) return batch_err(b, rc, c->msg);
+        b->n[k] = c->n;
+        b->nmax = std::max(b->nmax, c->n);
+        b->h_D[k] = c->D;
+        // row k: ifirst[0 .. n-2] (the total behind the last level), the total again up to the row's end
+        long long *row = b->h_if + (size_t)k * b->stride;
+        const int last = std::max(c->n - 2, 0);
+        for (int t = 0; t < b->stride; ++t) row[t] = c->n >= 3 ? c->ifirst[std::min(t, last)] : 0;
+    }
+    PBCHK(b, hipMemcpyAsync(b->d_D, b->h_D, (size_t)count * sizeof(PfDev), hipMemcpyHostToDevice, st));
+    PBCHK(b, hipMemcpyAsync(b->d_if, b->h_if, (size_t)K * b->stride * sizeof(long long), hipMemcpyHostToDevice, st));
+    b->count = count;
+    return CCJ_OK;
+}
+
+int batch_items(const ccj_pf_batch *b, int k, int t) {
+    const ccj_pf_ctx *c = b->mem[k];
+    return t >= 0 && t <= c->n - 3 ? (int)(c->ifirst[t + 1] - c->ifirst[t]) : 0;
+}
+
+int batch_fill_impl(ccj_pf_batch *b) {
+    if (b->count < 1) return batch_err(b, CCJ_E_STATE, "ccj_pf_batch_fill: no sequences bound");
+    ccj_pf_ctx *g = &b->model;  // the batch's graph: its streams and events
+    const int count = b->count, n = b->nmax;
+    const int *ns = b->n.data();
+    for (int k = 0; k < count; ++k) b->mem[k]->filled = false;
+    b->rc.assign(b->mem.size(), CCJ_E_STATE);
+    b->launches = 0;
+    PBCHK(b, hipSetDevice(g->device));
+    // every kernel launch of the fill goes through here
+    auto launch = [&](auto &&go) -> hipError_t {
+        int launched = 0;
+        const hipError_t e = (hipError_t)go(&launched);
+        b->launches += launched;
+        return e;
+    };
+    PBCHK(b, launch([&](int *l) { *l = 1; return ccjk_pf_zero_many(b->d_D, n, count, g->st); }));
+    PBCHK(b, hipEventRecord(g->e0, g->st));
+    // fill_impl's graph for the longest member n: level t after k_pf_iloop(t) and the spans <= t-1;
+    // k_pf_iloop(t+2) and the span t+3 (its P pushes first) after level t.  A shorter member's
+    // levels and spans carry the same indices, so the same edges order them.
+    const int nl = n - 2;
+    std::vector<int> items((size_t)count);
+    auto span = [&](int s) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (s >= 3) e = launch([&](int *l) { return ccjk_pf_ppush_many(b->d_D, ns, count, s - 3, g->st_d, l); });
+        if (e == hipSuccess) e = launch([&](int *l) { return ccjk_pf_diag_many(b->d_D, ns, count, s, g->st_d, l); });
+        return e != hipSuccess ? e : hipEventRecord(g->ev_dg[s], g->st_d);
+    };
+    auto iloop = [&](int t) -> hipError_t {
+        for (int k = 0; k < count; ++k) items[k] = batch_items(b, k, t);
+        const hipError_t e = launch([&](int *l) {
+            return ccjk_pf_iloop_many(b->d_D, ns, items.data(), count, b->d_if, b->stride, t, g->st_il, l);
+        });
+        return e != hipSuccess ? e : hipEventRecord(g->ev_il[t], g->st_il);
+    };
+    PBCHK(b, hipEventRecord(g->ev_start, g->st));
+    PBCHK(b, hipStreamWaitEvent(g->st_d, g->ev_start, 0));
+    PBCHK(b, hipStreamWaitEvent(g->st_il, g->ev_start, 0));
+    for (int s = 0; s <= std::min(2, n - 1); ++s) PBCHK(b, span(s));
+    for (int t = 0; t <= std::min(1, nl - 1); ++t) PBCHK(b, iloop(t));
+    for (int t = 0; t < nl; ++t) {
+        PBCHK(b, hipStreamWaitEvent(g->st, g->ev_il[t], 0));
+        if (t >= 1) PBCHK(b, hipStreamWaitEvent(g->st, g->ev_dg[t - 1], 0));
+        PBCHK(b, launch([&](int *l) { return ccjk_pf_level_many(b->d_D, ns, count, t, g->st, l); }));
+        PBCHK(b, hipEventRecord(g->ev_lev[t], g->st));
+        if (t + 2 < nl) {
+            PBCHK(b, hipStreamWaitEvent(g->st_il, g->ev_lev[t], 0));
+            PBCHK(b, iloop(t + 2));
+        }
+        if (t + 3 <= n - 1) {
+            PBCHK(b, hipStreamWaitEvent(g->st_d, g->ev_lev[t], 0));
+            PBCHK(b, span(t + 3));
+        }
+    }
+    PBCHK(b, hipStreamWaitEvent(g->st, g->ev_dg[n - 1], 0));
+    PBCHK(b, hipEventRecord(g->e1, g->st));
+    std::vector<std::vector<unsigned long long>> pabs((size_t)count);
+    for (int k = 0; k < count; ++k) {
+        ccj_pf_ctx *c = b->mem[k];
+        const size_t plane = c->plane();
+        c->h2d.assign((size_t)CCJ_PF_NMAT2 * plane, 0.0);
+        pabs[k].assign(plane, 0);
+        PBCHK(b, hipMemcpyAsync(c->h2d.data(), c->d_2d, c->h2d.size() * sizeof(double), hipMemcpyDeviceToHost, g->st));
+        PBCHK(b, hipMemcpyAsync(pabs[k].data(), c->d_Pabs, plane * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->st));
+    }
+    PBCHK(b, hipStreamSynchronize(g->st));
+    PBCHK(b, hipEventElapsedTime(&g->fill_ms, g->e0, g->e1));
+    for (int k = 0; k < count; ++k) {
+        ccj_pf_ctx *c = b->mem[k];
+        c->fill_ms = g->fill_ms;
+        b->rc[k] = finish_fill(c, pabs[k].data());  // CCJ_E_PF_RANGE: this member alone holds no fill
+    }
     return CCJ_OK;
 }
 
@@ -1510,8 +1822,11 @@ int ccj_pf_create_cap(const ccj_problem *prob, const ccj_pf_raw *raw, int device
     return create_any(prob, raw, device, capacity, out);
 }
 
+static const char *const kMemberMsg = "the context is a lockstep batch's member: the batch binds and fills it";
+
 int ccj_pf_rebind(ccj_pf_ctx *c, const char *seq) {
     if (!c) return CCJ_E_ARG;
+    if (c->batch) return pf_err(c, CCJ_E_STATE, kMemberMsg);
     try {
         return rebind_impl(c, seq);
     } catch (const std::bad_alloc &) {
@@ -1521,6 +1836,7 @@ int ccj_pf_rebind(ccj_pf_ctx *c, const char *seq) {
 
 int ccj_pf_reset(ccj_pf_ctx *c, const char *seq) {
     if (!c) return CCJ_E_ARG;
+    if (c->batch) return pf_err(c, CCJ_E_STATE, kMemberMsg);
     if (!seq || strlen(seq) != (size_t)c->n) return pf_err(c, CCJ_E_ARG, "ccj_pf_reset: the sequence must have the bound length");
     return ccj_pf_rebind(c, seq);
 }
@@ -1601,14 +1917,86 @@ int ccj_pf_setup_host_hashes(const ccj_problem *prob, const ccj_pf_raw *raw, uin
 }
 
 void ccj_pf_destroy(ccj_pf_ctx *c) {
-    if (!c) return;
+    if (!c || c->batch) return;  // a batch's member is freed by ccj_pf_batch_destroy
     hipSetDevice(c->device);
     free_dev(c);
     delete c;
 }
 
+int ccj_pf_batch_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int capacity, int members,
+                        ccj_pf_batch **out) {
+    if (!out) return CCJ_E_ARG;
+    *out = nullptr;
+    if (!prob || capacity < 1 || members < 1) {
+        g_batch_create_msg = "ccj_pf_batch_create: needs a problem, capacity >= 1 and members >= 1";
+        return CCJ_E_ARG;
+    }
+    ccj_pf_batch *b = new (std::nothrow) ccj_pf_batch();
+    if (!b) return CCJ_E_OOM;
+    b->model.device = device;
+    int rc;
+    try {
+        rc = batch_create_impl(prob, raw, device, capacity, members, b);
+    } catch (const std::bad_alloc &) {
+        rc = batch_err(b, CCJ_E_OOM, "host allocation failed");
+    }
+    if (rc != CCJ_OK) {
+        g_batch_create_msg = b->msg;
+        batch_free(b);
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return CCJ_OK;
+}
+
+int ccj_pf_batch_bind(ccj_pf_batch *b, const char *const *seqs, int count) {
+    if (!b) return CCJ_E_ARG;
+    try {
+        return batch_bind_impl(b, seqs, count);
+    } catch (const std::bad_alloc &) {
+        return batch_err(b, CCJ_E_OOM, "host allocation failed");
+    }
+}
+
+int ccj_pf_batch_fill(ccj_pf_batch *b) {
+    if (!b) return CCJ_E_ARG;
+    try {
+        return batch_fill_impl(b);
+    } catch (const std::bad_alloc &) {
+        return batch_err(b, CCJ_E_OOM, "host allocation failed");
+    }
+}
+
+int ccj_pf_batch_result(ccj_pf_batch *b, int k, double *energy) {
+    if (!b || k < 0 || k >= b->count) return CCJ_E_ARG;
+    if (b->rc[k] == CCJ_OK && energy) *energy = b->mem[k]->energy;
+    return b->rc[k];
+}
+
+ccj_pf_ctx *ccj_pf_batch_member(ccj_pf_batch *b, int k) { return b && k >= 0 && k < (int)b->mem.size() ? b->mem[k] : nullptr; }
+int ccj_pf_batch_members(const ccj_pf_batch *b) { return b ? (int)b->mem.size() : 0; }
+int ccj_pf_batch_count(const ccj_pf_batch *b) { return b ? b->count : 0; }
+double ccj_pf_batch_fill_ms(const ccj_pf_batch *b) { return b ? (double)b->model.fill_ms : 0.0; }
+int ccj_pf_batch_launches(const ccj_pf_batch *b) { return b ? b->launches : 0; }
+
+int ccj_pf_batch_item_counts(const ccj_pf_batch *b, int t, int *out) {
+    if (!b || !out) return CCJ_E_ARG;
+    for (int k = 0; k < b->count; ++k) out[k] = batch_items(b, k, t);
+    return CCJ_OK;
+}
+
+const char *ccj_pf_batch_last_error(const ccj_pf_batch *b) { return b ? b->msg.c_str() : g_batch_create_msg.c_str(); }
+
+void ccj_pf_batch_destroy(ccj_pf_batch *b) {
+    if (!b) return;
+    batch_free(b);
+    delete b;
+}
+
 int ccj_pf_fill(ccj_pf_ctx *c, double *energy) {
     if (!c) return CCJ_E_ARG;
+    if (c->batch) return pf_err(c, CCJ_E_STATE, kMemberMsg);
     const int rc = fill_impl(c);
     if (rc != CCJ_OK) return rc;
     if (energy) *energy = c->energy;
@@ -1790,6 +2178,7 @@ int ccj_pf_timing(ccj_pf_ctx *c, float *fill_ms) {
 
 int ccj_pf_set_timing(ccj_pf_ctx *c, int on) {
     if (!c) return CCJ_E_ARG;
+    if (c->batch) return pf_err(c, CCJ_E_STATE, kMemberMsg);  // a batch's launches are not per member
     c->timing = on != 0;
     return CCJ_OK;
 }

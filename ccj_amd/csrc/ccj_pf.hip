@@ -32,6 +32,9 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "ccj_pf_energy.h"
 #include "ccj_pf_engine.h"
 
@@ -206,7 +209,7 @@ __device__ __forceinline__ long long pf_pk_base(const PfDev &D, int t) {
 __device__ __forceinline__ int pf_G(int m, int h) { return h * m - ((h * (h - 1)) >> 1); }
 
 template <int U>
-__global__ __launch_bounds__(256) void k_pf_ppush(PfDev D, int lev, int ngrp, int npairs, int hs_len, int blocksA) {
+__device__ __forceinline__ void pf_ppush_body(const PfDev &D, int lev, int ngrp, int npairs, int hs_len, int blocksA) {
     const int n = D.n, rs = D.rs;
     const int lane = threadIdx.x & 63;
     const int partB = (int)blockIdx.x >= blocksA;
@@ -390,7 +393,7 @@ __device__ __forceinline__ double ordered_sum_deep(double acc, int N, int lane, 
     return acc;
 }
 
-__global__ __launch_bounds__(64) void k_pf_diag(PfDev D, int s) {
+__device__ __forceinline__ void pf_diag_body(const PfDev &D, int s) {
     const PfG G{D};
     const PfExp &E = *D.E;
     const int i = blockIdx.x + 1, j = i + s, n = D.n;
@@ -515,10 +518,7 @@ __global__ __launch_bounds__(64) void k_pf_diag(PfDev D, int s) {
 // The split loops run over s = d - i (or d - k):
 //   X1(s) = X(i+s, j, k, l)   X2(s) = X(i, i+s, k, l)   X3(s) = X(i, j, k+s, l)   X4(s) = X(i, j, k, k+s)
 // ---------------------------------------------------------------------------------------------
-#ifdef CCJ_PF_LEVEL_WAVES
-__attribute__((amdgpu_waves_per_eu(CCJ_PF_LEVEL_WAVES)))
-#endif
-__global__ __launch_bounds__(256) void k_pf_level(PfDev D, int t) {
+__device__ __forceinline__ void pf_level_body(const PfDev &D, int t) {
     const PfG G{D};
     const PfExp &E = *D.E;
     const int n = D.n, a = blockIdx.y, b = t - a, m = n - t - 2, rs = D.rs;
@@ -965,7 +965,7 @@ __device__ __forceinline__ double window_row(double r, uint32_t mk, const double
 // descriptor (once per wave) plus the u1 row's terms (once per row).  A candidate then costs two
 // readlanes and one vector address add; as a dependent descriptor load plus 64-bit index arithmetic
 // per candidate the kernel was bound by its scalar instruction stream.
-__global__ __launch_bounds__(256) void k_pf_iloop(PfDev D, int t, long long first, int nitems) {
+__device__ __forceinline__ void pf_iloop_body(const PfDev &D, int t, long long first, int nitems) {
     const int wv = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (wv >= nitems) return;
     const int lane = threadIdx.x & 63;
@@ -1082,6 +1082,175 @@ __global__ __launch_bounds__(256) void k_pf_canon(PfDev D, int x, const long lon
     for (int l = k; l <= D.n; ++l) out[q0 + (l - k)] = G.g4(x, i, j, k, l);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Kernel entries of the fill.  The single-context entries pass their by-value PfDev to the bodies
+// above and launch exactly as before.  The batched entries (ccj_pf_batch) run the
+// same bodies for every bound member of a lockstep batch in one launch: the member index is a grid
+// dimension of its own (z for k_pf_level, y for the others), so it is block-uniform, and the
+// member's PfDev comes from a device array through the constant address space, so its fields stay
+// scalar loads.  The other grid extents are the maximum over the members (ccj_pf_level_plan): a
+// block whose member lacks the level or span, or that lies beyond the member's own extent, leaves
+// as a whole block before it touches anything (no body has a barrier or LDS).  Per-member step
+// arguments are not kernel arguments: k_pf_iloop's (first, nitems) come from the table bind writes
+// (row k: member k's ifirst[]), k_pf_ppush's ngrp / npairs / blocksA from D.n as ccjk_pf_ppush
+// computes them.  k_pf_pterm (CCJ_PF_PULL=1) has no batched entry: a batch always pushes.
+// ---------------------------------------------------------------------------------------------
+template <int U>
+__global__ __launch_bounds__(256) void k_pf_ppush(PfDev D, int lev, int ngrp, int npairs, int hs_len, int blocksA) {
+    pf_ppush_body<U>(D, lev, ngrp, npairs, hs_len, blocksA);
+}
+__global__ __launch_bounds__(64) void k_pf_diag(PfDev D, int s) { pf_diag_body(D, s); }
+#ifdef CCJ_PF_LEVEL_WAVES
+__attribute__((amdgpu_waves_per_eu(CCJ_PF_LEVEL_WAVES)))
+#endif
+__global__ __launch_bounds__(256) void k_pf_level(PfDev D, int t) { pf_level_body(D, t); }
+__global__ __launch_bounds__(256) void k_pf_iloop(PfDev D, int t, long long first, int nitems) {
+    pf_iloop_body(D, t, first, nitems);
+}
+
+namespace {
+
+// member k's PfDev: wave-uniform scalar loads (nothing writes the array while a fill runs)
+// (word by word: a memcpy from the constant address space is lowered to vector loads, and every
+// pointer of the member would then live in vector registers)
+struct PfDevWords { unsigned long long w[sizeof(PfDev) / 8]; };
+static_assert(sizeof(PfDev) % 8 == 0 && sizeof(PfDevWords) == sizeof(PfDev), "PfDev is read as 64-bit words");
+__device__ __forceinline__ PfDev ldc_dev(const PfDev *Ds, unsigned k) {
+    const auto *q = (const __attribute__((address_space(4))) unsigned long long *)(unsigned long long)(Ds + k);
+    PfDevWords W;
+#pragma unroll
+    for (unsigned x = 0; x < sizeof(PfDev) / 8; ++x) W.w[x] = q[x];
+    return __builtin_bit_cast(PfDev, W);
+}
+
+// k_pf_ppush's launch arithmetic for one length (ccjk_pf_ppush, ccj_pf_level_plan and
+// k_pf_ppush_many share it): false when the level pushes nothing
+constexpr int PF_PP_HS = 32;  // h steps per work item
+__host__ __device__ __forceinline__ bool pf_ppush_geom(int n, int lev, int &ngrp, int &npairs, int &blocksA) {
+    const int nmax = imin(lev, n - 4 - lev) + 1;
+    if (lev < 0 || nmax <= 0) return false;
+    ngrp = (n - lev - 3 + 63) / 64;
+    const int nch = (nmax + PF_PP_S - 1) / PF_PP_S;
+    npairs = 0;
+    for (int c = 0; c < nch; ++c) npairs += (imin((c + 1) * PF_PP_S, nmax) + PF_PP_HS - 1) / PF_PP_HS;
+    blocksA = (npairs * ngrp * (lev + 1) + 3) / 4;
+    return true;
+}
+
+}  // namespace
+
+template <int U>
+__global__ __launch_bounds__(256) void k_pf_ppush_many(const PfDev *Ds, int lev) {
+    const PfDev D = ldc_dev(Ds, blockIdx.y);
+    int ngrp, npairs, blocksA;
+    if (!pf_ppush_geom(D.n, lev, ngrp, npairs, blocksA) || (int)blockIdx.x >= 2 * blocksA) return;
+    pf_ppush_body<U>(D, lev, ngrp, npairs, PF_PP_HS, blocksA);
+}
+__global__ __launch_bounds__(64) void k_pf_diag_many(const PfDev *Ds, int s) {
+    const PfDev D = ldc_dev(Ds, blockIdx.y);
+    if ((int)blockIdx.x + 1 + s > D.n) return;
+    pf_diag_body(D, s);
+}
+#ifdef CCJ_PF_LEVEL_WAVES
+__attribute__((amdgpu_waves_per_eu(CCJ_PF_LEVEL_WAVES)))
+#endif
+__global__ __launch_bounds__(256) void k_pf_level_many(const PfDev *Ds, int t) {
+    const PfDev D = ldc_dev(Ds, blockIdx.z);
+    if (t > D.n - 3) return;  // the member has no level t (its descriptor would be stale)
+    const int m = D.n - t - 2;
+    if ((int)blockIdx.x * 256 >= m * (m + 1) / 2) return;
+    pf_level_body(D, t);
+}
+// ifirst: row k (stride doubles as the row length) = member k's first item of every level, its
+// total behind the last level
+__global__ __launch_bounds__(256) void k_pf_iloop_many(const PfDev *Ds, const long long *__restrict__ ifirst, int stride, int t) {
+    const PfDev D = ldc_dev(Ds, blockIdx.y);
+    if (t > D.n - 3) return;
+    const long long *row = ifirst + (size_t)blockIdx.y * stride;
+    const long long first = row[t];
+    const int nitems = (int)(row[t + 1] - first);
+    if ((int)blockIdx.x * 4 >= nitems) return;
+    pf_iloop_body(D, t, first, nitems);
+}
+
+// Zero what a fill accumulates into, for every member in one launch: the 8 2-D planes, Pacc, Pabs
+// over the member's bound plane ((n+1) * rs).
+__global__ __launch_bounds__(256) void k_pf_zero_many(const PfDev *Ds) {
+    const PfDev D = ldc_dev(Ds, blockIdx.y);
+    const int plane = (D.n + 1) * D.rs;
+    for (int q = blockIdx.x * 256 + threadIdx.x; q < plane; q += gridDim.x * 256) {
+        D.V[q] = 0.0; D.VM[q] = 0.0; D.WM[q] = 0.0; D.WMv[q] = 0.0;
+        D.WMp[q] = 0.0; D.WBP[q] = 0.0; D.WPP[q] = 0.0; D.P[q] = 0.0;
+        D.Pacc[q] = 0;
+        D.Pabs[q] = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Launch geometry, host only (ccj_pf_level_plan, include/ccj_pf.h).  With level t the fill's graph
+// enqueues k_pf_iloop(t+2), k_pf_level(t), k_pf_ppush(t) and k_pf_diag(t+3); t = -3, -2, -1 are
+// the launches ahead of level 0 (the spans 0..2, the iloops of levels 0 and 1).  grid4[f] is the
+// grid one sequence of length n launches for family f alone, {0,0,0} = no launch.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct PfGrid { int x, y, z; };
+
+void pf_alone(int n, int t, int nitems, PfGrid g[4]) {
+    for (int f = 0; f < 4; ++f) g[f] = PfGrid{0, 0, 0};
+    const int ti = t + 2;  // k_pf_iloop: a wave per item
+    if (ti >= 0 && ti <= n - 3) {
+        if (nitems < 0) g[0] = PfGrid{-1, -1, -1};
+        else if (nitems > 0) g[0] = PfGrid{(nitems + 3) / 4, 1, 1};
+    }
+    if (t >= 0 && t <= n - 3) {  // k_pf_level: 256 cells of one a-block
+        const int m = n - t - 2, M = m * (m + 1) / 2;
+        if (M > 0) g[1] = PfGrid{(M + 255) / 256, t + 1, 1};
+    }
+    int ngrp, npairs, blocksA;
+    if (t >= 0 && pf_ppush_geom(n, t, ngrp, npairs, blocksA)) g[2] = PfGrid{2 * blocksA, 1, 1};
+    const int s = t + 3;  // k_pf_diag: a wave per interval
+    if (s >= 0 && n - s > 0) g[3] = PfGrid{n - s, 1, 1};
+}
+
+// the batched grids: the member dimension is y (z for k_pf_level), the others the members' maxima
+void pf_joint(const int *n, const int *nitems, int count, int t, PfGrid g[4], PfGrid *per /* [count][4] or null */) {
+    for (int f = 0; f < 4; ++f) g[f] = PfGrid{0, 0, 0};
+    bool unknown = false;
+    for (int k = 0; k < count; ++k) {
+        PfGrid a[4];
+        pf_alone(n[k], t, nitems ? nitems[k] : -1, a);
+        for (int f = 0; f < 4; ++f) {
+            if (per) per[k * 4 + f] = a[f];
+            if (a[f].x < 0) unknown = true;
+            else if (a[f].x > 0) g[f] = PfGrid{std::max(g[f].x, a[f].x), f == 1 ? a[f].y : count, f == 1 ? count : 1};
+        }
+    }
+    if (unknown) g[0] = PfGrid{-1, -1, -1};
+}
+
+}  // namespace
+
+extern "C" int ccj_pf_level_plan_items(const int *n, const int *nitems, int count, int t, int *out) {
+    if (!n || !out || count < 1) return CCJ_E_ARG;
+    int nmax = 0;
+    for (int k = 0; k < count; ++k) {
+        if (n[k] < 1 || n[k] > 1023 || (nitems && nitems[k] < 0)) return CCJ_E_ARG;
+        nmax = std::max(nmax, n[k]);
+    }
+    if (t < -3 || t > nmax - 3) return CCJ_E_ARG;
+    PfGrid g[4];
+    std::vector<PfGrid> per((size_t)count * 4);
+    pf_joint(n, nitems, count, t, g, per.data());
+    for (int f = 0; f < 4; ++f) out[3 * f] = g[f].x, out[3 * f + 1] = g[f].y, out[3 * f + 2] = g[f].z;
+    for (int q = 0; q < count * 4; ++q) out[12 + 3 * q] = per[q].x, out[12 + 3 * q + 1] = per[q].y, out[12 + 3 * q + 2] = per[q].z;
+    return CCJ_OK;
+}
+
+extern "C" int ccj_pf_level_plan(const int *n, int count, int t, int *out) {
+    return ccj_pf_level_plan_items(n, nullptr, count, t, out);
+}
+
 extern "C" int ccjk_pf_pterm(const PfDev *D, int s, void *stream) {
 #ifdef CCJ_ABLATE_PF_PTERM
     return 0;  // timing only: this PF kernel skipped (wrong results)
@@ -1093,29 +1262,34 @@ extern "C" int ccjk_pf_pterm(const PfDev *D, int s, void *stream) {
     return (int)hipGetLastError();
 }
 
+// The launches of the fill.  Every grid comes from pf_alone / pf_joint, the functions behind
+// ccj_pf_level_plan; the single-context wrappers launch what they always did.
+namespace {
+// split steps in flight per k_pf_ppush wave (CCJ_PF_PP_STEPS, default 4; 2 for the A/B)
+int pf_pp_steps() {
+    static const int steps = getenv("CCJ_PF_PP_STEPS") ? atoi(getenv("CCJ_PF_PP_STEPS")) : 4;
+    return steps;
+}
+dim3 pf_dim(const PfGrid &g) { return dim3((unsigned)g.x, (unsigned)g.y, (unsigned)g.z); }
+}  // namespace
+
 // P terms whose operands' highest level is lev (k_pf_ppush); completes P(lev+3).  The grid as
 // ccjk_ppush's (MFE) for one rank.
 extern "C" int ccjk_pf_ppush(const PfDev *D, int lev, void *stream) {
 #ifdef CCJ_ABLATE_PF_PTERM
     return 0;  // timing only: this PF kernel skipped (wrong results)
 #endif
-    const int n = D->n;
-    const int nmax = imin(lev, n - 4 - lev) + 1;
-    if (nmax <= 0) return 0;
-    const int ngrp = (n - lev - 3 + 63) / 64;
-    constexpr int hs_len = 32;
-    const int nch = (nmax + PF_PP_S - 1) / PF_PP_S;
-    int npairs = 0;
-    for (int c = 0; c < nch; ++c) npairs += (imin((c + 1) * PF_PP_S, nmax) + hs_len - 1) / hs_len;
-    const int blocksA = (npairs * ngrp * (lev + 1) + 3) / 4;
-    // split steps in flight per wave (CCJ_PF_PP_STEPS, default 4; 2 for the A/B)
-    static const int steps = getenv("CCJ_PF_PP_STEPS") ? atoi(getenv("CCJ_PF_PP_STEPS")) : 4;
-    if (steps >= 4)
-        hipLaunchKernelGGL((k_pf_ppush<4>), dim3((unsigned)(2 * blocksA)), dim3(256), 0, (hipStream_t)stream, *D, lev, ngrp,
-                           npairs, hs_len, blocksA);
+    PfGrid g[4];
+    pf_alone(D->n, lev, -1, g);
+    if (g[2].x <= 0) return 0;
+    int ngrp, npairs, blocksA;
+    pf_ppush_geom(D->n, lev, ngrp, npairs, blocksA);
+    if (pf_pp_steps() >= 4)
+        hipLaunchKernelGGL((k_pf_ppush<4>), pf_dim(g[2]), dim3(256), 0, (hipStream_t)stream, *D, lev, ngrp, npairs, PF_PP_HS,
+                           blocksA);
     else
-        hipLaunchKernelGGL((k_pf_ppush<2>), dim3((unsigned)(2 * blocksA)), dim3(256), 0, (hipStream_t)stream, *D, lev, ngrp,
-                           npairs, hs_len, blocksA);
+        hipLaunchKernelGGL((k_pf_ppush<2>), pf_dim(g[2]), dim3(256), 0, (hipStream_t)stream, *D, lev, ngrp, npairs, PF_PP_HS,
+                           blocksA);
     return (int)hipGetLastError();
 }
 
@@ -1123,17 +1297,19 @@ extern "C" int ccjk_pf_diag(const PfDev *D, int s, void *stream) {
 #ifdef CCJ_ABLATE_PF_DIAG
     return 0;  // timing only: this PF kernel skipped (wrong results)
 #endif
-    const int ni = D->n - s;
-    if (ni <= 0) return 0;
-    hipLaunchKernelGGL(k_pf_diag, dim3((unsigned)ni), dim3(64), 0, (hipStream_t)stream, *D, s);
+    PfGrid g[4];
+    pf_alone(D->n, s - 3, -1, g);
+    if (g[3].x <= 0) return 0;
+    hipLaunchKernelGGL(k_pf_diag, pf_dim(g[3]), dim3(64), 0, (hipStream_t)stream, *D, s);
     return (int)hipGetLastError();
 }
 
 extern "C" int ccjk_pf_level(const PfDev *D, const PfLvl *Lh, int t, void *stream) {
-    const int M = Lh[t].M;
-    if (M <= 0) return 0;
-    hipLaunchKernelGGL(k_pf_level, dim3((unsigned)((M + 255) / 256), (unsigned)(t + 1)), dim3(256), 0, (hipStream_t)stream,
-                       *D, t);
+    (void)Lh;
+    PfGrid g[4];
+    pf_alone(D->n, t, -1, g);
+    if (g[1].x <= 0) return 0;
+    hipLaunchKernelGGL(k_pf_level, pf_dim(g[1]), dim3(256), 0, (hipStream_t)stream, *D, t);
     return (int)hipGetLastError();
 }
 
@@ -1141,9 +1317,61 @@ extern "C" int ccjk_pf_iloop(const PfDev *D, int t, long long first, int nitems,
 #ifdef CCJ_ABLATE_PF_ILOOP
     return 0;  // timing only: this PF kernel skipped (wrong results)
 #endif
-    if (nitems <= 0) return 0;
-    hipLaunchKernelGGL(k_pf_iloop, dim3((unsigned)((nitems + 3) / 4)), dim3(256), 0, (hipStream_t)stream, *D, t, first,
-                       nitems);
+    PfGrid g[4];
+    pf_alone(D->n, t - 2, std::max(nitems, 0), g);
+    if (g[0].x <= 0) return 0;
+    hipLaunchKernelGGL(k_pf_iloop, pf_dim(g[0]), dim3(256), 0, (hipStream_t)stream, *D, t, first, nitems);
+    return (int)hipGetLastError();
+}
+
+// The batched launches: Ds = the device array of the bound members' PfDev, n[count] their lengths
+// (host).  *launched = 1 when a kernel was enqueued (some member has work at this step).
+extern "C" int ccjk_pf_ppush_many(const PfDev *Ds, const int *n, int count, int lev, void *stream, int *launched) {
+    PfGrid g[4];
+    pf_joint(n, nullptr, count, lev, g, nullptr);
+    *launched = g[2].x > 0;
+    if (!*launched) return 0;
+    if (pf_pp_steps() >= 4)
+        hipLaunchKernelGGL((k_pf_ppush_many<4>), pf_dim(g[2]), dim3(256), 0, (hipStream_t)stream, Ds, lev);
+    else
+        hipLaunchKernelGGL((k_pf_ppush_many<2>), pf_dim(g[2]), dim3(256), 0, (hipStream_t)stream, Ds, lev);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_pf_diag_many(const PfDev *Ds, const int *n, int count, int s, void *stream, int *launched) {
+    PfGrid g[4];
+    pf_joint(n, nullptr, count, s - 3, g, nullptr);
+    *launched = g[3].x > 0;
+    if (!*launched) return 0;
+    hipLaunchKernelGGL(k_pf_diag_many, pf_dim(g[3]), dim3(64), 0, (hipStream_t)stream, Ds, s);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_pf_level_many(const PfDev *Ds, const int *n, int count, int t, void *stream, int *launched) {
+    PfGrid g[4];
+    pf_joint(n, nullptr, count, t, g, nullptr);
+    *launched = g[1].x > 0;
+    if (!*launched) return 0;
+    hipLaunchKernelGGL(k_pf_level_many, pf_dim(g[1]), dim3(256), 0, (hipStream_t)stream, Ds, t);
+    return (int)hipGetLastError();
+}
+
+// nitems[count]: each member's items of level t (host; 0 where it lacks the level); ifirst: the
+// device table k_pf_iloop_many reads them from, rows of `stride`
+extern "C" int ccjk_pf_iloop_many(const PfDev *Ds, const int *n, const int *nitems, int count, const long long *ifirst,
+                                  int stride, int t, void *stream, int *launched) {
+    PfGrid g[4];
+    pf_joint(n, nitems, count, t - 2, g, nullptr);
+    *launched = g[0].x > 0;
+    if (!*launched) return 0;
+    hipLaunchKernelGGL(k_pf_iloop_many, pf_dim(g[0]), dim3(256), 0, (hipStream_t)stream, Ds, ifirst, stride, t);
+    return (int)hipGetLastError();
+}
+
+extern "C" int ccjk_pf_zero_many(const PfDev *Ds, int nmax, int count, void *stream) {
+    const int plane = (nmax + 1) * (nmax + 2);
+    hipLaunchKernelGGL(k_pf_zero_many, dim3((unsigned)((plane + 255) / 256), (unsigned)count), dim3(256), 0,
+                       (hipStream_t)stream, Ds);
     return (int)hipGetLastError();
 }
 

@@ -98,4 +98,18 @@ int ccjk_pf_diag(const ccj::PfDev *D, int s, void *stream);
 int ccjk_pf_level(const ccj::PfDev *D, const ccj::PfLvl *Lh, int t, void *stream);
 int ccjk_pf_iloop(const ccj::PfDev *D, int t, long long first, int nitems, void *stream);
 int ccjk_pf_canon(const ccj::PfDev *D, int x, const long long *rowoff, int nrows, int *out, void *stream);
+// The batched launches of a lockstep batch (ccj_pf_batch): one launch runs the step for every
+// bound member.  Ds: the device array of the members' PfDev; n[count]: their lengths (host).  The
+// grids are ccj_pf_level_plan's; *launched = 1 when some member has work and a kernel was
+// enqueued.  k_pf_iloop_many reads each member's (first, nitems) from row k of the device table
+// ifirst (rows of `stride`: member k's first item of every level, its total behind the last);
+// nitems[count] are the same counts on the host, for the grid.  There is no batched k_pf_pterm
+// (CCJ_PF_PULL=1): a batch always pushes its P terms.
+int ccjk_pf_ppush_many(const ccj::PfDev *Ds, const int *n, int count, int lev, void *stream, int *launched);
+int ccjk_pf_diag_many(const ccj::PfDev *Ds, const int *n, int count, int s, void *stream, int *launched);
+int ccjk_pf_level_many(const ccj::PfDev *Ds, const int *n, int count, int t, void *stream, int *launched);
+int ccjk_pf_iloop_many(const ccj::PfDev *Ds, const int *n, const int *nitems, int count, const long long *ifirst,
+                       int stride, int t, void *stream, int *launched);
+// zero the 2-D planes, Pacc and Pabs of every member (one launch)
+int ccjk_pf_zero_many(const ccj::PfDev *Ds, int nmax, int count, void *stream);
 }

@@ -119,6 +119,65 @@ int ccj_pf_setup_hashes(ccj_pf_ctx *ctx, uint64_t *out, int cap);
  * entry (direct5) and through the key tables and the gather functions the kernels share (keyed5). */
 int ccj_pf_setup_host_hashes(const ccj_problem *prob, const ccj_pf_raw *raw, uint64_t *direct5, uint64_t *keyed5);
 
+/* Lockstep batch — the partition function's ccj_batch (ccj.h): `members`
+ * capacity contexts for the lengths 1..capacity whose fills run in ONE set of level launches, so a
+ * set of short sequences pays the launch chain of its longest member once.
+ *
+ * ccj_pf_batch_create builds the Boltzmann tables and the key tables once and shares them among the
+ * members (prob->seq may be NULL).  Its up-front size check compares members x
+ * ccj_pf_footprint(capacity) plus the shared tables with the device's free memory (CCJ_E_OOM with a
+ * message, before anything is allocated); members < 1 or capacity < 1 is CCJ_E_ARG.
+ *
+ * ccj_pf_batch_bind gives member k the sequence seqs[k] (1 <= count <= members, each of length
+ * 1..capacity over A/C/G/U/T); the other members idle.  A bad argument is CCJ_E_ARG before any
+ * member is touched: the previous binding stays usable.  The per-sequence setup is ccj_pf_rebind's,
+ * enqueued for all members on the batch's stream with one host wait (the item counts of all
+ * members).  After bind no member holds a fill.
+ *
+ * ccj_pf_batch_fill zeroes every member's sums in one launch, enqueues ccj_pf_fill's event graph once,
+ * sized for the longest bound member, with each kernel launched once per level or span for all
+ * members (k_pf_*_many; always the pushed P terms, CCJ_PF_PULL is not read), then per member copies
+ * the 2-D planes back, runs the exactness check (CCJ_PF_RANGE_LOG2 as in ccj_pf_fill) and forms W and
+ * the energy on the host.  A member whose check fails holds no fill: ccj_pf_batch_result gives
+ * CCJ_E_PF_RANGE for it (ccj_pf_last_message on the member has the text); the other members are
+ * untouched and the call still returns CCJ_OK.  A HIP error fails the whole call.
+ *
+ * ccj_pf_batch_member is borrowed: after a fill it is in the state ccj_pf_fill leaves, so ccj_pf_W,
+ * _get2, _get4, _hashes, _exp_hashes, _setup_hashes, _srand, _sample, _n, _capacity and _work_model
+ * work on it; its own ccj_pf_rebind, _reset, _fill and _set_timing return CCJ_E_STATE, and
+ * ccj_pf_destroy ignores it.  ccj_pf_batch_launches: the kernel launches the last fill enqueued (the
+ * zeroing launch and every k_pf_*_many launch of the graph); ccj_pf_batch_item_counts: each bound
+ * member's k_pf_iloop items of level t (0 where it has no such level), what ccj_pf_level_plan_items
+ * takes.  ccj_pf_batch_last_error(NULL): the message of the last failed create. */
+typedef struct ccj_pf_batch ccj_pf_batch;
+int ccj_pf_batch_create(const ccj_problem *prob, const ccj_pf_raw *raw, int device, int capacity, int members,
+                        ccj_pf_batch **out);
+int ccj_pf_batch_bind(ccj_pf_batch *b, const char *const *seqs, int count);
+int ccj_pf_batch_fill(ccj_pf_batch *b);
+int ccj_pf_batch_result(ccj_pf_batch *b, int k, double *energy);
+ccj_pf_ctx *ccj_pf_batch_member(ccj_pf_batch *b, int k);
+int ccj_pf_batch_members(const ccj_pf_batch *b);
+int ccj_pf_batch_count(const ccj_pf_batch *b);
+double ccj_pf_batch_fill_ms(const ccj_pf_batch *b);
+int ccj_pf_batch_launches(const ccj_pf_batch *b);
+int ccj_pf_batch_item_counts(const ccj_pf_batch *b, int t, int *out);
+const char *ccj_pf_batch_last_error(const ccj_pf_batch *b);
+void ccj_pf_batch_destroy(ccj_pf_batch *b);
+
+/* The launch geometry of a fill, host only (no GPU).  With level t the fill's graph enqueues four
+ * launches: k_pf_iloop(t+2), k_pf_level(t), k_pf_ppush(t), k_pf_diag(t+3); t = -3, -2, -1 are the
+ * launches ahead of level 0 (the spans 0..2 and the iloops of levels 0 and 1), so t runs from -3 to
+ * the longest member's last level max(n) - 3 (anything else, a length outside 1..1023 or count < 1
+ * is CCJ_E_ARG).  For members of lengths n[count], out receives 12 + 12 * count ints: the grid
+ * (x, y, z) of each of the four launches in that order, then per member the four grids that member
+ * would launch alone.  {0,0,0} = no launch.  In a joint grid the member dimension (z for
+ * k_pf_level, y for the others) is count and every other extent is the maximum over the members;
+ * for count == 1 it is the single context's launch.  k_pf_iloop's extent depends on the sequence:
+ * ccj_pf_level_plan_items takes each member's item count of level t+2 (ccj_pf_batch_item_counts);
+ * without them (ccj_pf_level_plan) that family is reported as {-1,-1,-1} wherever the level exists. */
+int ccj_pf_level_plan(const int *n, int count, int t, int *out);
+int ccj_pf_level_plan_items(const int *n, const int *nitems, int count, int t, int *out);
+
 /* ccj_pf(): the whole fill on the GPU, then W on the host.  *energy = to_Energy(W[n], n)
  * (part_func.cc:148-150,173). */
 int ccj_pf_fill(ccj_pf_ctx *ctx, double *energy);
