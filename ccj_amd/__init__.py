@@ -22,6 +22,7 @@ __all__ = [
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
     "pf_many", "PfLockstepBatch", "pf_level_plan", "PF_PLAN_KERNELS", "pf_setup_host_hashes", "PF_SETUP_TABLES", "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
+    "il_prune_host", "IL_U",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -281,6 +282,12 @@ def lib() -> ctypes.CDLL:
         L.ccj_pf_batch_destroy.restype = None
         L.ccj_pf_level_plan_items.argtypes = [ctypes.POINTER(ip), ctypes.POINTER(ip), ip, ip, ctypes.POINTER(ip)]
         L.ccj_pf_level_plan_items.restype = ip
+    # (likewise the candidate-list pruning, absent from an older tree's library)
+    if hasattr(L, "ccj_il_counts"):
+        L.ccj_il_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong)]
+        L.ccj_il_counts.restype = ip
+        L.ccj_il_prune_host.argtypes = [ctypes.POINTER(_Problem), ctypes.POINTER(ctypes.c_longlong)] + [vp] * 6
+        L.ccj_il_prune_host.restype = ip
     L.ccj_pf_fill.argtypes = [vp, dp]
     L.ccj_pf_fill.restype = ip
     L.ccj_pf_W.argtypes = [vp, dp]
@@ -321,6 +328,42 @@ def num_cells(n: int) -> int:
         return 0
     m = n + 1
     return m * (m - 1) * (m - 2) * (m - 3) // 24
+
+
+IL_U = 29  # ccj_engine.h IE_U: u1, u2 in [0, 28]
+
+
+def il_prune_host(seq: str, params: str | bytes = "Turner04", dangle: int = 2, noGU: bool = False, pen=None,
+                  windows: bool = True):
+    """The candidate-list pruning rule on the host, no GPU (include/ccj.h ccj_il_prune_host).
+
+    Returns a dict: ``counts`` = (il kept, il full, ilm kept, ilm full) and, with ``windows``, the numpy
+    arrays ``e_il``, ``e_ilm`` (int16) and ``st_il``, ``st_ilm`` (uint8), each [w][p][u1][u2] with p in
+    [0, n+2), and the planes ``est``, ``ie`` [w][p]: see the header for the status values."""
+    import numpy as np
+    blob = params if isinstance(params, (bytes, bytearray)) else load_params(params)
+    blob_buf = ctypes.create_string_buffer(bytes(blob), len(blob))
+    seq_buf = ctypes.create_string_buffer(seq.encode())
+    pk = None
+    if pen is not None:
+        pk = _Penalties(*[int(v) for v in pen[:12]], float(pen[12]), float(pen[13]))
+    prob = _Problem(ctypes.cast(seq_buf, ctypes.c_char_p), dangle, 1 if noGU else 0, ctypes.cast(blob_buf, ctypes.c_void_p),
+                    ctypes.cast(ctypes.pointer(pk), ctypes.c_void_p) if pk is not None else None)
+    n = len(seq)
+    counts = (ctypes.c_longlong * 4)()
+    out = {}
+    ptrs = [None] * 6
+    if windows:
+        shape = (n + 1, n + 2, IL_U, IL_U)
+        for x, (name, dt, sh) in enumerate([("e_il", np.int16, shape), ("e_ilm", np.int16, shape), ("st_il", np.uint8, shape),
+                                            ("st_ilm", np.uint8, shape), ("est", np.int16, shape[:2]), ("ie", np.int16, shape[:2])]):
+            out[name] = np.zeros(sh, dtype=dt)
+            ptrs[x] = out[name].ctypes.data_as(ctypes.c_void_p)
+    rc = lib().ccj_il_prune_host(ctypes.byref(prob), counts, *ptrs)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "ccj_il_prune_host")
+    out["counts"] = tuple(counts)
+    return out
 
 
 def param_path(name_or_path: str) -> str:
@@ -494,6 +537,13 @@ class W_final:
         bit-identity.  Non-zero after a RangeError, and after a fold that CCJ_ALLOW_OUT_OF_RANGE=1 let
         complete under the engine's clamp-only semantics."""
         return lib().ccj_range_flags(self._h)
+
+    def il_counts(self):
+        """(il kept, il full, ilm kept, ilm full): entries of the last fill's interior-loop candidate
+        lists after and before pruning (include/ccj.h ccj_il_counts; CCJ_IL_PRUNE=0 keeps them all)."""
+        out = (ctypes.c_longlong * 4)()
+        self._check(lib().ccj_il_counts(self._h, out))
+        return tuple(out)
 
     def fill(self):
         self._check(lib().ccj_fill(self._h))

@@ -273,12 +273,13 @@ struct DevTables {
     const LvlX *ldx;
     // interior-loop candidate lists (k_build_il): per pair [w][p], the (u1,u2) whose inner pair can
     // pair, ordered by dt = 2+u1+u2 then u1; entry .x = dt << 21 | u1 << 16 | (uint16)energy,
-    // .y = 2*u1*dt (the address cross term); IL_B null entries (dt 63) follow the last one
+    // .y = 2*u1*dt (the address cross term); IL_B null entries (dt 63) follow the last one.  Entries
+    // dominated through a stacked pair are left out (ccj_ilprune.h; CCJ_IL_PRUNE=0 keeps them)
     uint2 *il, *ilm;               // il: pair (p,p+w) closes the loop (PL, PR); ilm: pair encloses (PM)
     int16_t *dummy;                // n+64 values 32767: target of the null entries
     const uint32_t *items;         // k_iloop work items (role << 30 | f1 << 20 | f2 << 10 | chunk)
     int full4;                     // 1: a full context, d4 has all 22 slots per level (mslot); 0: the NMAT_D4 first
-    uint32_t *ilseg, *ilmseg;      // [pair][IL_SEG]
+    uint32_t *ilseg, *ilmseg;      // [pair][IL_SEG]; word 0 (no dt < 2 exists): the entry count before pruning
     int *err;                      // device error word
     // split-point sharing (above): levels [g_lo, g_hi) share; partial-record ring of SHARE_R
     // slots x SHARE_NACC x accC

@@ -35,6 +35,7 @@
 #include "ccj_backtrack.h"
 #include "ccj_traceback.h"
 #include "ccj_items.h"
+#include "ccj_ilprune.h"
 
 using namespace ccj;
 
@@ -2238,6 +2239,115 @@ extern "C" int ccj_work_model_seq(const char *seq, int noGU, double *out) {
     const int rc = work_model(n, S.data(), pairt, w);
     for (int x = 0; x < 4; ++x) out[x] = w[x];
     return rc;
+}
+
+// Kept and full entry counts of the last fill's candidate lists (k_build_il; seg[IL_SEG-1] and
+// seg[0] of every pair that can pair): out4 = il kept, il full, ilm kept, ilm full.
+extern "C" int ccj_il_counts(ccj_ctx *c, long long *out4) {
+    if (!c || !out4) return CCJ_E_ARG;
+    if (!c->filled) return set_err(c, CCJ_E_STATE, "ccj_il_counts before a fill");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t plane = (size_t)(c->n + 1) * c->rs;
+    std::vector<uint32_t> seg(plane * IL_SEG);
+    for (int kind = 0; kind < 2; ++kind) {
+        HIPCHK(c, hipMemcpy(seg.data(), kind ? c->d_ilmseg : c->d_ilseg, seg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        long long kept = 0, full = 0;
+        for (int w = 0; w < c->n; ++w)
+            for (int p = 1; p + w <= c->n; ++p) {
+                const size_t x = (size_t)w * c->rs + p;
+                if (c->hpt_h[x] <= 0) continue;  // no list is built for a pair that cannot pair
+                kept += seg[x * IL_SEG + IL_SEG - 1];
+                full += seg[x * IL_SEG];
+            }
+        out4[2 * kind] = kept;
+        out4[2 * kind + 1] = full;
+    }
+    return CCJ_OK;
+}
+
+// The pruning rule of the candidate lists on the host, no GPU (ccj_ilprune.h: the functions
+// k_build_il runs).  Planes are [w][p] with row stride n+2, (n+1)(n+2) elements; windows are
+// [plane][IE_U][IE_U] = [..][u1][u2].  Any output may be NULL.
+//   counts4: il kept, il full, ilm kept, ilm full over the pairs that can pair (as ccj_il_counts)
+//   e_il / e_ilm: the window energies (0 outside the list)
+//   st_il / st_ilm: 0 = not in the list, 1 = kept, 1 | 2 * (IL_NEAR | IL_FAR bits) = dropped
+//   est, ie: the two planes the rule reads
+extern "C" int ccj_il_prune_host(const ccj_problem *prob, long long *counts4, int16_t *e_il, int16_t *e_ilm, uint8_t *st_il,
+                                 uint8_t *st_ilm, int16_t *est_out, int16_t *ie_out) {
+    if (!prob || !prob->seq || !prob->params) return CCJ_E_ARG;
+    const int n = (int)strlen(prob->seq), rs = n + 2;
+    if (n < 1 || prob->params->magic != CCJ_PARAMS_MAGIC || prob->params->size_bytes != sizeof(ccj_energy_params)) return CCJ_E_ARG;
+    ccj_pk_penalties pk = CCJ_PK_PENALTIES_DEFAULT;
+    if (prob->pen) pk = *prob->pen;
+    int8_t pair[64], rtype[8] = {0, 2, 1, 4, 3, 6, 5, 7};
+    for (int x = 0; x < 8; ++x)
+        for (int y = 0; y < 8; ++y) pair[x * 8 + y] = (int8_t)BP_PAIR[x][y];
+    if (prob->noGU) pair[3 * 8 + 4] = pair[4 * 8 + 3] = 0;
+    for (int x = 0; x < 8; ++x)
+        for (int y = 0; y < 8; ++y) rtype[pair[x * 8 + y]] = pair[y * 8 + x];
+    std::vector<short> S(n + 2, 0), S1(n + 2, 0);
+    for (int i = 1; i <= n; ++i) S[i] = S1[i] = (short)encode_base(prob->seq[i - 1]);
+    S[n + 1] = S[1], S[0] = (short)n, S1[n + 1] = S1[1], S1[0] = S1[n];
+    std::vector<int> lx((size_t)2 * n + 64, 0);
+    for (size_t x = 31; x < lx.size(); ++x) lx[x] = (int)(prob->params->lxc * log((double)x / 30.));
+    const size_t plane = (size_t)(n + 1) * rs;
+    std::vector<int8_t> pt(plane, 0);
+    std::vector<int16_t> est(plane, (int16_t)INTERN_INF), ie(plane, (int16_t)INTERN_INF);
+    const IlHostTables T{n, rs, S.data(), S1.data(), pt.data(), pair, rtype, prob->params, lx.data(), pk.e_intP, est.data(), ie.data()};
+    bool bad = false;
+    for (int w = 0; w < n; ++w)
+        for (int p = 1; p + w <= n; ++p) {
+            const int q = p + w;
+            const size_t x = (size_t)w * rs + p;
+            pt[x] = pair[S[p] * 8 + S[q]];
+            if (q - p >= 2 && p + 1 != q - 1) {  // get_e_stP as seq_setup saturates it
+                const int t2 = pair[S[p + 1] * 8 + S[q - 1]];
+                const long v = lrint(pk.e_stP * E_IntLoop(prob->params, lx.data(), 0, 0, pt[x], rtype[t2], S1[p + 1], S1[q - 1], S1[p], S1[q]));
+                if (v < -32768 || (pt[x] > 0 && t2 > 0 && v >= INTERN_INF)) bad = true;
+                est[x] = (int16_t)(v >= INTERN_INF ? INTERN_INF : v);
+            }
+            const int v = il_eint_raw(T, 0, 0, p, q);  // k_precompute_ie
+            if (v != INTERN_INF && !il_e_in_range(v)) bad = true;
+            ie[x] = (int16_t)v;
+        }
+    if (bad) return CCJ_E_PARAMS;
+    long long cnt[4] = {0, 0, 0, 0};
+    int es[IE_U][IE_U];
+    bool in[IE_U][IE_U];
+    for (int kind = 0; kind < 2; ++kind) {
+        int16_t *eo = kind ? e_ilm : e_il;
+        uint8_t *so = kind ? st_ilm : st_il;
+        if (eo) memset(eo, 0, plane * IE_U * IE_U * sizeof(int16_t));
+        if (so) memset(so, 0, plane * IE_U * IE_U);
+        for (int w = 0; w < n; ++w)
+            for (int p = 1; p + w <= n; ++p) {
+                const size_t x = (size_t)w * rs + p;
+                if (pt[x] <= 0) continue;
+                const int q = p + w;
+                for (int u1 = 0; u1 < IE_U; ++u1)
+                    for (int u2 = 0; u2 < IE_U; ++u2) {
+                        es[u1][u2] = 0;
+                        in[u1][u2] = il_window(T, kind, p, q, u1, u2, es[u1][u2]);
+                        if (in[u1][u2] && !il_e_in_range(es[u1][u2])) return CCJ_E_PARAMS;
+                    }
+                for (int u1 = 0; u1 < IE_U; ++u1)
+                    for (int u2 = 0; u2 < IE_U; ++u2) {
+                        if (!in[u1][u2]) continue;
+                        const int dom = (u1 && u2) ? il_dominated(T, kind, p, q, u1, u2, es[u1][u2], in[0][0], es[0][0],
+                                                                  in[u1 - 1][u2 - 1], es[u1 - 1][u2 - 1])
+                                                   : 0;
+                        cnt[2 * kind] += dom == 0;
+                        cnt[2 * kind + 1] += 1;
+                        const size_t o = (x * IE_U + u1) * IE_U + u2;
+                        if (eo) eo[o] = (int16_t)es[u1][u2];
+                        if (so) so[o] = (uint8_t)(1 | 2 * dom);
+                    }
+            }
+    }
+    if (counts4) memcpy(counts4, cnt, sizeof cnt);
+    if (est_out) memcpy(est_out, est.data(), plane * sizeof(int16_t));
+    if (ie_out) memcpy(ie_out, ie.data(), plane * sizeof(int16_t));
+    return CCJ_OK;
 }
 
 extern "C" int ccj_host_timing(const ccj_ctx *c, double *out3) {

@@ -23,6 +23,7 @@
 #include "ccj_engine.h"
 #include "ccj_energy.h"
 #include "ccj_items.h"
+#include "ccj_ilprune.h"
 
 using namespace ccj;
 
@@ -229,12 +230,10 @@ __global__ void k_init2d_many(const DevTables *__restrict__ tabs) {
 __device__ __forceinline__ int e_intP(const DevTables &T, int u1, int u2, int p, int q) {
     const int d = p + u1 + 1, dp = q - u2 - 1;
     if (dp - d < 1) return INTERN_INF;
-    const int t1 = T.pair[T.S[p] * 8 + T.S[q]];
-    const int t2 = T.pair[T.S[d] * 8 + T.S[dp]];
-    if (t1 <= 0 || t2 <= 0) return INTERN_INF;  // the reference only visits candidates with can_pair() on both pairs
-    const int e = E_IntLoop(T.prm, T.lx, u1, u2, t1, T.rtype[t2], T.S1[p + 1], T.S1[q - 1], T.S1[d - 1], T.S1[dp + 1]);
-    const int v = (int)rint(T.e_intP * (double)e);
-    if (v < -32768 || v >= INTERN_INF) atomicOr(T.err, 1);
+    // the reference only visits candidates with can_pair() on both pairs
+    if (T.pair[T.S[p] * 8 + T.S[q]] <= 0 || T.pair[T.S[d] * 8 + T.S[dp]] <= 0) return INTERN_INF;
+    const int v = il_eint_raw(T, u1, u2, p, q);  // ccj_ilprune.h: shared with the pruning rule
+    if (!il_e_in_range(v)) atomicOr(T.err, 1);
     return v;
 }
 
@@ -811,9 +810,11 @@ __global__ __launch_bounds__(256) void k_ppush_many(const DevTables *__restrict_
 // Only candidates whose other pair can pair are kept (the reference skips the rest: can_pair),
 // in order of dt = 2+u1+u2 (the source level distance), u1 ascending; seg[dt] is the first entry
 // of dt.  One wave per pair: the window's validity and energies are gathered at once (lane = u1)
-// into LDS, then compacted per dt (lane = u1, ballot).
+// into LDS, then compacted per dt (lane = u1, ballot).  Between the two, with prune set, the entries
+// that are dominated through a stacked pair are cleared (ccj_ilprune.h): k_iloop never
+// reads them, and no stored value changes.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void build_il_body(const DevTables &T, int kind) {
+__device__ __forceinline__ void build_il_body(const DevTables &T, int kind, int prune) {
     __shared__ int16_t es[IE_U][IE_U + 1];  // [u1][u2]: the window's energies
     __shared__ uint32_t vb[IE_U];            // [u1]: bit u2 = the candidate is kept
     const int n = T.n, rs = T.rs;
@@ -853,9 +854,32 @@ __device__ __forceinline__ void build_il_body(const DevTables &T, int kind) {
         vb[u1] = bits;
     }
     __syncthreads();
+    // the full list's entry count, kept in seg[0] (no entry has dt < 2; ccj_il_counts reads it)
+    int full = lane < IE_U ? __popc(vb[lane]) : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) full += __shfl_xor(full, o, 64);
+    if (prune) {
+        // Drop the entries dominated through a stacked pair (ccj_ilprune.h): no cell's minimum
+        // needs them.  The rule reads the window as built, so the bits are cleared only after
+        // every lane has evaluated its row.
+        uint32_t dom = 0;
+        if (lane >= 1 && lane < IE_U) {
+            const int u1 = lane;
+            const uint32_t mine = vb[u1], prev = vb[u1 - 1];
+            const bool v00 = vb[0] & 1u;
+            const int e00 = es[0][0];
+            for (int u2 = 1; u2 < IE_U; ++u2)
+                if (((mine >> u2) & 1u) &&
+                    il_dominated(T, kind, p, q, u1, u2, es[u1][u2], v00, e00, (prev >> (u2 - 1)) & 1u, es[u1 - 1][u2 - 1]))
+                    dom |= 1u << u2;
+        }
+        __syncthreads();
+        if (lane < IE_U) vb[lane] &= ~dom;
+        __syncthreads();
+    }
     int cnt = 0;
     for (int dt = 0; dt < IL_SEG; ++dt) {
-        if (lane == 0) seg[dt] = (uint32_t)cnt;
+        if (lane == 0) seg[dt] = dt ? (uint32_t)cnt : (uint32_t)full;
         const int u1 = lane, u2 = dt - 2 - lane;
         const bool valid = dt >= 2 && u1 < IE_U && u2 >= 0 && u2 < IE_U && ((vb[u1] >> u2) & 1u);
         const unsigned long long mask = __ballot(valid);
@@ -867,9 +891,9 @@ __device__ __forceinline__ void build_il_body(const DevTables &T, int kind) {
     // null tail: dt 63 addresses the sentinel pad (32767), energy 32767 -> 65534, never below a clamped result
     if (lane < IL_B) ent[cnt + lane] = make_uint2((63u << 21) | (uint32_t)INTERN_INF, 0u);
 }
-__global__ __launch_bounds__(64) void k_build_il(DevTables T) { build_il_body(T, (int)blockIdx.z); }
-__global__ __launch_bounds__(64) void k_build_il_many(const DevTables *__restrict__ tabs) {  // z = 2 * member + kind
-    build_il_body(tabs[blockIdx.z >> 1], (int)(blockIdx.z & 1));
+__global__ __launch_bounds__(64) void k_build_il(DevTables T, int prune) { build_il_body(T, (int)blockIdx.z, prune); }
+__global__ __launch_bounds__(64) void k_build_il_many(const DevTables *__restrict__ tabs, int prune) {  // z = 2 * member + kind
+    build_il_body(tabs[blockIdx.z >> 1], (int)(blockIdx.z & 1), prune);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2246,10 +2270,17 @@ extern "C" int ccjk_ppush(const DevTables *T, int lev, int G, int rank, void *st
     return (int)hipGetLastError();
 }
 
+// CCJ_IL_PRUNE=0 (read at call time) keeps the full candidate lists: the A side of an A/B run, and
+// the tests' yardstick for the pruned fill
+static int il_prune_on() {
+    const char *e = getenv("CCJ_IL_PRUNE");
+    return !(e && atoi(e) == 0);
+}
+
 extern "C" int ccjk_build_il(const DevTables *T, void *stream) {
     const int n = T->n;
     if (n < 1) return 0;
-    hipLaunchKernelGGL(k_build_il, dim3(n, n + 1, 2), dim3(64), 0, (hipStream_t)stream, *T);
+    hipLaunchKernelGGL(k_build_il, dim3(n, n + 1, 2), dim3(64), 0, (hipStream_t)stream, *T, il_prune_on());
     return (int)hipGetLastError();
 }
 
@@ -2626,7 +2657,7 @@ extern "C" int ccjk_pre_many(const DevTables *tabs, int count, int nmax, void *s
     const int total = (nmax + 1) * (nmax + 2);
     hipLaunchKernelGGL(k_init2d_many, dim3((total + 255) / 256, count), dim3(256), 0, s, tabs);
     hipLaunchKernelGGL(k_precompute_ie_many, dim3((nmax + 255) / 256, nmax + 1, count), dim3(256), 0, s, tabs);
-    hipLaunchKernelGGL(k_build_il_many, dim3(nmax, nmax + 1, 2 * count), dim3(64), 0, s, tabs);
+    hipLaunchKernelGGL(k_build_il_many, dim3(nmax, nmax + 1, 2 * count), dim3(64), 0, s, tabs, il_prune_on());
     return (int)hipGetLastError();
 }
 

@@ -356,6 +356,21 @@ int  ccj_pmpo2d_low(int n, const int *wbp, int bp, int cp, int *out6);
  * disagrees with ccj_pmpo2d_closed's evaluator at some valid cell. */
 int  ccj_pmpo2d_low_brute(int n, const int *wbp, int bp, int cp, int valid_only, int *out6);
 
+/* Interior-loop candidate lists: the list builder drops the candidates that are
+ * dominated through a stacked pair, which changes no stored value.  CCJ_IL_PRUNE=0 in the
+ * environment (read when a fill is enqueued) keeps the full lists.
+ * ccj_il_counts: after a fill, out4 = kept and full entry counts of the context's il lists (PL, PR),
+ * then of its ilm lists (PM), over the pairs that can pair.
+ * ccj_il_prune_host: the same rule on the host, no GPU, for prob's sequence, parameters and penalties.
+ * Planes are [w][p] = w*(n+2)+p over (n+1)(n+2) elements; windows are plane x 29 x 29, [u1][u2].
+ * counts4 as ccj_il_counts; e_il / e_ilm: each list entry's e_intP energy; st_il / st_ilm: 0 = not in
+ * the list, 1 = kept, 3 / 5 / 7 = dropped (through the pair stacked on the list's own pair / on the
+ * candidate's pair / either); est, ie: the e_stP plane and the e_intP plane of the loop without
+ * unpaired bases.  Any output may be NULL. */
+int  ccj_il_counts(ccj_ctx *ctx, long long *out4);
+int  ccj_il_prune_host(const ccj_problem *prob, long long *counts4, int16_t *e_il, int16_t *e_ilm, uint8_t *st_il,
+                       uint8_t *st_ilm, int16_t *est, int16_t *ie);
+
 #ifdef __cplusplus
 }
 #endif
