@@ -22,7 +22,7 @@ __all__ = [
     "DEFAULT_SPLIT_TARGET", "LocalGroup", "W_final_pf", "PF_MAT4", "PF_MAT2", "layout_extents", "fold_many",
     "SampleExit", "pf_exp_hashes", "load_pfraw", "LockstepBatch", "batch_level_plan", "BatchLevelPlan", "plan_lockstep",
     "pf_many", "PfLockstepBatch", "pf_level_plan", "PF_PLAN_KERNELS", "pf_setup_host_hashes", "PF_SETUP_TABLES", "RangeError", "RANGE_LEVEL", "RANGE_ILOOP", "RANGE_PARTIAL", "RANGE_TAB", "RANGE_CF", "RANGE_EXIT_CODE",
-    "il_prune_host", "IL_U",
+    "il_prune_host", "IL_U", "share_roles", "ShareRoles", "SideRole",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -212,6 +212,9 @@ def lib() -> ctypes.CDLL:
     L.ccj_level_schedule.restype = ip
     L.ccj_ctx_level_schedule.argtypes = [vp, ip, ip, ctypes.POINTER(ip)]
     L.ccj_ctx_level_schedule.restype = ip
+    if hasattr(L, "ccj_share_roles"):  # not in a CCJ_LIB_VARIANT built from an older tree (A/B runs)
+        L.ccj_share_roles.argtypes = [ip, ip, ip, ip, ip, ctypes.POINTER(ip)]
+        L.ccj_share_roles.restype = ip
     # lockstep batch
     L.ccj_batch_create.argtypes = [ctypes.POINTER(_Problem), ctypes.POINTER(_Options), ip, ip, ctypes.POINTER(vp)]
     L.ccj_batch_create.restype = ip
@@ -863,6 +866,40 @@ def level_schedule(n: int, t: int, world: int = 1, rank: int = 0, split_target: 
     if rc != CCJ_OK:
         raise CCJError(rc, "bad schedule arguments")
     return LevelSchedule((bool(out[0]), out[1], out[2], out[3], out[4]))
+
+
+class SideRole(tuple):
+    """One side (a-loop or b-loop) of a cell's split-point sharing (include/ccj.h ccj_share_roles):
+    role (0 full scan, 1 leader, 2 follower), low, top (the split points 1 .. low and the top `top`
+    of its range the cell scans itself), cuts (a leader's cut for followers r = 1, 2, 3)."""
+    __slots__ = ()
+    role = property(lambda s: s[0])
+    low = property(lambda s: s[1])
+    top = property(lambda s: s[2])
+    cuts = property(lambda s: s[3])
+
+
+class ShareRoles(tuple):
+    """a-block a of level t: a_side, b_side (SideRole), in_lead (k_level4d_lead runs the block),
+    sharing, g_lo, g_hi."""
+    __slots__ = ()
+    a_side = property(lambda s: s[0])
+    b_side = property(lambda s: s[1])
+    in_lead = property(lambda s: s[2])
+    sharing = property(lambda s: s[3])
+    g_lo = property(lambda s: s[4])
+    g_hi = property(lambda s: s[5])
+
+
+def share_roles(n: int, t: int, a: int, split_target: int = DEFAULT_SPLIT_TARGET, edges: bool = True) -> ShareRoles:
+    """The sharing roles of a-block a of level t (no GPU needed; include/ccj.h ccj_share_roles).
+    split_target is the resolved target: 0 = never split (what the option's -1 means)."""
+    out = (ctypes.c_int * 16)()
+    rc = lib().ccj_share_roles(n, t, a, split_target, 1 if edges else 0, out)
+    if rc != CCJ_OK:
+        raise CCJError(rc, "bad role arguments")
+    sides = [SideRole((out[o], out[o + 1], out[o + 2], (out[o + 3], out[o + 4], out[o + 5]))) for o in (0, 6)]
+    return ShareRoles((sides[0], sides[1], bool(out[12]), bool(out[13]), out[14], out[15]))
 
 
 def layout_extents(n: int, split_target: int = DEFAULT_SPLIT_TARGET, share: bool = True, full4: bool = False,

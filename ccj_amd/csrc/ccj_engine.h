@@ -145,6 +145,33 @@ constexpr int SHARE_NACC = 4;
 constexpr int SHARE_SLOTS = SHARE_R;
 enum AccRec { AI = 0, AJ = 1, AK = 2, AL = 3 };
 
+// The sharing role of one side of a cell, written once for level4d_body, the host's leader lists
+// and ccj_share_roles.  len is the side's own gap (a for the a-loop, b for the b-loop), oth the
+// other gap, t = len + oth the level, grp whether level t shares.
+//   role 0: the cell scans its whole range 1..len;  1: leader, scans 1..len for itself and its
+//   followers;  2: follower r = len % SHARE_R of the leader at level t-r, gap len-r.
+// The cell itself scans the split points 1..low and len-top+1..len.  A leader's term for follower r
+// at split point s reads a W operand of span s+r-1, which k_diag2d has finished before level t only
+// for s <= len+oth-r: the leader leaves the top share_cut(r, oth) = max(0, r-oth) split points out of
+// that follower's partial (the points 1..len-cut are in it), and the follower scans them itself at
+// its own level, where they are its top min(cut, len-r) points.  (The cut cannot be one smaller
+// because the last point is masked anyway: for cut = 2 the point below the last is not available
+// either.)  edges = 0 keeps the rule this replaced: a column whose other gap is below SHARE_R-1
+// does not share at all (CCJ_SHARE_EDGES=0, A/B runs).  A follower whose leader would lie below
+// g_lo has none and scans in full.
+struct ShareRole {
+    int role, low, top;
+};
+__host__ __device__ __forceinline__ int share_cut(int r, int oth) { return r > oth ? r - oth : 0; }
+__host__ __device__ __forceinline__ ShareRole share_role(bool grp, int edges, int len, int oth, int g_lo) {
+    const int r = len % SHARE_R;
+    if (!grp || (!edges && oth < SHARE_R - 1)) return ShareRole{0, len, 0};
+    if (r == 0) return ShareRole{1, len, 0};
+    if (len + oth - r < g_lo) return ShareRole{0, len, 0};
+    const int cut = share_cut(r, oth);
+    return ShareRole{2, r, cut < len - r ? cut : len - r};
+}
+
 // Band sharding: a-block a of every level belongs to rank (a / SHARD_GRP) % world,
 // the same rank on every level, so a split-sharing leader (a % SHARE_R == 0) and its followers
 // (a+1 .. a+SHARE_R-1, later levels) always live on one rank.  A rank's blocks are numbered by
@@ -287,6 +314,7 @@ struct DevTables {
     long long xpad;                // 32767 sentinel elements in front of every level's PLx/PRx and PMx (k_iloop's null target)
     long long xspan;               // bytes k_iloop may address from a wave's buffer base (debug check)
     int g_lo, g_hi;
+    int share_edges;               // 1: columns with a short other gap share too (share_role; CCJ_SHARE_EDGES=0: 0)
     // k_level4d_lead walks only the long-scan a-blocks of a sharing level, longest scan first:
     // rank r's list lord[lord_off[t*G+r] .. lord_off[t*G+r+1]) (device), lord_off_h = the same
     // offsets on the host
@@ -389,22 +417,21 @@ inline void sched_share_range(int n, int split_target, bool share, int &g_lo, in
 }
 
 // Does k_level4d_lead run a-block a of sharing level t (a leader or a full scan on either side;
-// the roles of level4d_body)?  cost: its scan cost, a leader step at about 2.5 plain steps.  A
-// follower whose leader would lie below g_lo (t - ra < g_lo) has none and scans its full range.
-inline bool sched_lead_block(int t, int a, int g_lo, double *cost) {
-    const int b = t - a, ra = a % SHARE_R, rb = b % SHARE_R;
-    const int ar = b >= SHARE_R - 1 ? (ra == 0 ? 1 : (t - ra >= g_lo ? 2 : 0)) : 0;
-    const int br = a >= SHARE_R - 1 ? (rb == 0 ? 1 : (t - rb >= g_lo ? 2 : 0)) : 0;
-    if (ar == 2 && br == 2) return false;
-    if (cost) *cost = (ar == 1 ? 2.5 : 1.0) * (ar == 2 ? ra : a) + (br == 1 ? 2.5 : 1.0) * (br == 2 ? rb : b);
+// the roles of level4d_body, share_role)?  cost: the split steps its cells scan themselves, a leader
+// step at about 2.5 plain steps, a follower its low and top points.
+inline bool sched_lead_block(int t, int a, int g_lo, int edges, double *cost) {
+    const int b = t - a;
+    const ShareRole ar = share_role(true, edges, a, b, g_lo), br = share_role(true, edges, b, a, g_lo);
+    if (ar.role == 2 && br.role == 2) return false;
+    if (cost) *cost = (ar.role == 1 ? 2.5 : 1.0) * (ar.low + ar.top) + (br.role == 1 ? 2.5 : 1.0) * (br.low + br.top);
     return true;
 }
 
 // rank r's blocks of level t that k_level4d_lead runs (the length of its lord list)
-inline int sched_lead_count(int t, int G, int r, int g_lo, int g_hi) {
+inline int sched_lead_count(int t, int G, int r, int g_lo, int g_hi, int edges) {
     if (t < g_lo || t >= g_hi) return 0;
     int cnt = 0;
-    for (int a = 0; a <= t; ++a) cnt += shard_owner(a, G) == r && sched_lead_block(t, a, g_lo, nullptr);
+    for (int a = 0; a <= t; ++a) cnt += shard_owner(a, G) == r && sched_lead_block(t, a, g_lo, edges, nullptr);
     return cnt;
 }
 
@@ -414,8 +441,8 @@ struct LevelSched {
     int lead_split;  // k_level4d_lead's waves per chunk (0: rank r launches no leader block)
 };
 
-// lead_nblk: the length of rank r's lord list at t (< 0: count it)
-inline LevelSched level_sched(int n, int t, int G, int r, int split_target, int g_lo, int g_hi, int lead_nblk) {
+// lead_nblk: the length of rank r's lord list at t (< 0: count it, under the edge rule `edges`)
+inline LevelSched level_sched(int n, int t, int G, int r, int split_target, int g_lo, int g_hi, int lead_nblk, int edges = 1) {
     LevelSched s{0, 0, 0};
     if (n - t - 2 <= 0 || t < 0) return s;
     s.sharing = t >= g_lo && t < g_hi;
@@ -423,7 +450,7 @@ inline LevelSched level_sched(int n, int t, int G, int r, int split_target, int 
     // on the sharing levels the plain launch only has follower cells (short scans): never split
     if (own > 0) s.split = s.sharing ? 1 : sched_level_split(n, t, own, split_target);
     if (!s.sharing) return s;
-    if (lead_nblk < 0) lead_nblk = sched_lead_count(t, G, r, g_lo, g_hi);
+    if (lead_nblk < 0) lead_nblk = sched_lead_count(t, G, r, g_lo, g_hi, edges);
     if (lead_nblk <= 0) return s;
     // each leader chunk's scans are split over lead_split waves of one workgroup (the barriers
     // inside the leader scans need every wave of the workgroup on the same chunk)

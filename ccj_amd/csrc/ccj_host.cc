@@ -139,6 +139,7 @@ struct ccj_ctx {
     bool host_tb = false;                   // W + traceback on the host over the mirror (else on the GPU)
     int split_target = 9216;                // k_level4d split heuristic (0: never split)
     bool share = true;                      // split-point sharing
+    int share_edges = 1;                    // ... also in the columns with a short other gap (CCJ_SHARE_EDGES)
     // fill timing (ccj_set_timing, CCJ_LEVEL_TIMING): 0 = fill only; 1 = + level durations from the
     // lev_done events the fill records anyway (no extra packets); 2 = + a marker pair around every
     // kernel family launch (k_diag2d, k_iloop, the level span).  The markers of mode 2 are barrier
@@ -809,6 +810,15 @@ static int seq_setup(ccj_ctx *c) {
     return CCJ_OK;
 }
 
+// CCJ_SHARE_EDGES=0 (read where a schedule is resolved: a context's creation, the context-free
+// schedule and layout exports) keeps the columns with a short other gap out of split-point sharing
+// (ccj_engine.h share_role): the A side of an A/B run.  The host lists and the kernels both follow
+// the context's value (DevTables::share_edges).
+static int share_edges_env() {
+    const char *e = getenv("CCJ_SHARE_EDGES");
+    return !(e && atoi(e) == 0);
+}
+
 // --------------------------------------------------------------------------------------------
 // The layout of one sequence length: every quantity the device buffers' sizes and offsets derive
 // from n (with the d4 slot count and the split target).  create_impl sizes every allocation from
@@ -824,7 +834,7 @@ struct Layout {
     std::vector<LvlX> ldx;
 };
 
-static void layout_build(int n, int nm4, int split_target, bool share, Layout &L) {
+static void layout_build(int n, int nm4, int split_target, bool share, int edges, Layout &L) {
     const int nent = std::max(n, 1);
     L = Layout{};
     L.n = n;
@@ -878,7 +888,7 @@ static void layout_build(int n, int nm4, int split_target, bool share, Layout &L
     sched_share_range(n, split_target, share, L.g_lo, L.g_hi);
     for (int t = L.g_lo; t < L.g_hi; ++t) {
         L.accC = std::max<long long>(L.accC, L.lv[t].C);
-        for (int a = 0; a <= t; ++a) L.nlord += sched_lead_block(t, a, L.g_lo, nullptr);
+        for (int a = 0; a <= t; ++a) L.nlord += sched_lead_block(t, a, L.g_lo, edges, nullptr);
     }
 }
 
@@ -906,11 +916,11 @@ static void layout_extents_of(const Layout &L, int G, long long *e) {
 // what a binding of n uses, or (as_capacity) what a context for every length 1 .. n allocates: the
 // entrywise maximum over those lengths (the sharing range, and with it the leader list and the
 // ring, moves with n and the split target, so those are not monotone in n)
-static std::vector<long long> layout_extents(int n, int G, int nm4, int split_target, bool share, bool as_capacity) {
+static std::vector<long long> layout_extents(int n, int G, int nm4, int split_target, bool share, int edges, bool as_capacity) {
     std::vector<long long> e(LX_N, 0), x(LX_N, 0);
     Layout L;
     for (int q = as_capacity ? 1 : n; q <= n; ++q) {
-        layout_build(q, nm4, split_target, share, L);
+        layout_build(q, nm4, split_target, share, edges, L);
         layout_extents_of(L, G, x.data());
         for (int k = 0; k < LX_N; ++k) e[k] = std::max(e[k], x[k]);
     }
@@ -922,7 +932,7 @@ extern "C" const char *ccj_layout_extent_names(void) { return LX_NAMES; }
 extern "C" int ccj_layout_extents(int n, int split_target, int share, int full4, int as_capacity, long long *out, int cap) {
     if (n < 1 || n > 1023 || split_target < 0 || (cap > 0 && !out)) return -CCJ_E_ARG;
     if (cap >= LX_N) {
-        const std::vector<long long> e = layout_extents(n, 1, full4 ? NMAT4 : NMAT_D4, split_target, share != 0, as_capacity != 0);
+        const std::vector<long long> e = layout_extents(n, 1, full4 ? NMAT4 : NMAT_D4, split_target, share != 0, share_edges_env(), as_capacity != 0);
         std::copy(e.begin(), e.end(), out);
     }
     return LX_N;
@@ -945,7 +955,7 @@ static int bind_layout(ccj_ctx *c, int n) {
     if (n < 1 || n > c->ncap) return set_err(c, CCJ_E_ARG, "length %d outside the context's capacity 1..%d", n, c->ncap);
     const int G = c->world;
     Layout L;
-    layout_build(n, c->nm4, c->split_target, c->share, L);
+    layout_build(n, c->nm4, c->split_target, c->share, c->share_edges, L);
     if ((uint64_t)L.ncell != (uint64_t)ccj_num_cells(n)) return set_err(c, CCJ_E_ARG, "layout size mismatch");
     long long e[LX_N];
     layout_extents_of(L, G, e);
@@ -973,7 +983,7 @@ static int bind_layout(ccj_ctx *c, int n) {
             blk.clear();
             for (int a = 0; a <= t; ++a) {
                 double cost = 0;
-                if (shard_owner(a, G) != r || !sched_lead_block(t, a, L.g_lo, &cost)) continue;
+                if (shard_owner(a, G) != r || !sched_lead_block(t, a, L.g_lo, c->share_edges, &cost)) continue;
                 blk.push_back({cost, a});
             }
             std::stable_sort(blk.begin(), blk.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
@@ -1025,6 +1035,7 @@ static int bind_layout(ccj_ctx *c, int n) {
     T.xspan = c->xspan;
     T.g_lo = L.g_lo;
     T.g_hi = L.g_hi;
+    T.share_edges = c->share_edges;
     T.acc = sharing ? c->d_acc : nullptr;
     T.lord = sharing ? c->d_lord : nullptr;
     T.lord_off = sharing ? c->d_lord_off : nullptr;
@@ -1078,6 +1089,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
         if (lt) c->level_timing = std::max(0, std::min(2, atoi(lt)));
         const char *g = getenv("CCJ_SHARE_SPLITS");
         c->share = !(g && atoi(g) < 0) && !(opts && opts->share_splits < 0);
+        c->share_edges = share_edges_env();
     }
     if (c->rank < 0 || c->rank >= c->world) return CCJ_E_ARG;
     memcpy(&c->prm, prob->params, sizeof(ccj_energy_params));
@@ -1114,7 +1126,7 @@ static int create_impl(const ccj_problem *prob, const ccj_options *opts, int nma
     c->full4 = c->exchanges() || c->overlap || (getenv("CCJ_D4_FULL") && atoi(getenv("CCJ_D4_FULL")) != 0);
     c->nm4 = c->full4 ? NMAT4 : NMAT_D4;
     // every allocation below is sized from the capacity's extents and nothing else
-    c->cap_ext = layout_extents(nmax, c->world, c->nm4, c->split_target, c->share, true);
+    c->cap_ext = layout_extents(nmax, c->world, c->nm4, c->split_target, c->share, c->share_edges, true);
     const std::vector<long long> &X = c->cap_ext;
     if (const int rc = span_check(c.get(), X.data(), nmax)) return rc;
     // (int)(lxc*log(x/30.)) with the host libm, as ViennaRNA computes it
@@ -2410,7 +2422,7 @@ extern "C" int ccj_level_schedule(int n, int t, int world, int rank, int split_t
     if (!out5 || n < 1 || world < 1 || rank < 0 || rank >= world || t < 0 || split_target < 0) return CCJ_E_ARG;
     int g_lo, g_hi;
     sched_share_range(n, split_target, share != 0, g_lo, g_hi);
-    const LevelSched s = level_sched(n, t, world, rank, split_target, g_lo, g_hi, -1);
+    const LevelSched s = level_sched(n, t, world, rank, split_target, g_lo, g_hi, -1, share_edges_env());
     out5[0] = s.sharing, out5[1] = s.split, out5[2] = s.lead_split, out5[3] = g_lo, out5[4] = g_hi;
     return CCJ_OK;
 }
@@ -2427,6 +2439,27 @@ extern "C" int ccj_ctx_level_schedule(const ccj_ctx *c, int t, int rank, int *ou
     const LevelSched s = level_sched(c->n, t, G, rank, c->split_target, g_lo, g_hi, lead_nblk);
     out7[0] = s.sharing, out7[1] = s.split, out7[2] = s.lead_split, out7[3] = g_lo, out7[4] = g_hi;
     out7[5] = c->split_target, out7[6] = c->share ? 1 : 0;
+    return CCJ_OK;
+}
+
+// The sharing roles of a-block a of level t (ccj_engine.h share_role: what level4d_body and the
+// leader lists use), without a context or a GPU.  Per side (a-loop at 0, b-loop at 6): role, the
+// split points the cell scans itself (low, top) and, for a leader, the cut of follower r = 1 .. 3;
+// then whether k_level4d_lead runs the block, whether level t shares, g_lo, g_hi.
+extern "C" int ccj_share_roles(int n, int t, int a, int split_target, int edges, int *out16) {
+    if (!out16 || n < 1 || t < 0 || a < 0 || a > t || n - t - 2 <= 0 || split_target < 0) return CCJ_E_ARG;
+    int g_lo, g_hi;
+    sched_share_range(n, split_target, true, g_lo, g_hi);
+    const bool grp = t >= g_lo && t < g_hi;
+    const int len[2] = {a, t - a};
+    for (int s = 0; s < 2; ++s) {
+        const ShareRole R = share_role(grp, edges != 0, len[s], len[1 - s], g_lo);
+        int *o = out16 + 6 * s;
+        o[0] = R.role, o[1] = R.low, o[2] = R.top;
+        for (int r = 1; r <= 3; ++r) o[2 + r] = R.role == 1 && r < SHARE_R ? share_cut(r, len[1 - s]) : 0;
+    }
+    out16[12] = grp && sched_lead_block(t, a, g_lo, edges != 0, nullptr);
+    out16[13] = grp, out16[14] = g_lo, out16[15] = g_hi;
     return CCJ_OK;
 }
 

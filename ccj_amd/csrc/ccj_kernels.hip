@@ -1463,17 +1463,35 @@ __device__ __forceinline__ void pipe_scan(int s, int step, int last, int mlim, L
 // 241 VGPRs instead of ~150 (2 waves/SIMD) and measured fill +5 ms.  (Peeling the
 // final, possibly masked, step so the other steps skip the mask adds — ~15% of a leader step's
 // VALU — measured fill +1.7 ms: 146 instead of 130 VGPRs, the leaders are not VALU-bound.)
+// The reduce gets the split point itself: a leader masks per follower (share_cut, ccj_engine.h).
 template <class V, class LD, class ST>
-__device__ __forceinline__ void pipe_scan_lead(int s, int step, int last, int mlim, LD ld, ST st) {
+__device__ __forceinline__ void pipe_scan_lead(int s, int step, int last, LD ld, ST st) {
     V cur = ld(s);
     for (;;) {
         const int sn = s + step;
         const V nxt = ld(imin(sn, last));
-        st(cur, s < mlim ? 0 : INF);
+        st(cur, s);
         if (sn > last) break;
         cur = nxt;
         s = sn;
     }
+}
+// A leader's scan of s = s0, s0+step, ... <= len as two runs of that loop: the main one over
+// s <= len - cutm (one mask for all followers, every W row finished: the loop as it was before the
+// short-gap columns shared) and the tail over the top cutm split points of a short-gap column
+// (per-follower masks, W rows clamped; cutm = share_cut(SHARE_R-1, other gap) <= 3, 0 in every
+// other column: no tail).  ld / st take the run as a std::bool_constant.
+template <class V, class LD, class ST>
+__device__ __forceinline__ void lead_scan(int s0, int step, int len, int cutm, LD ld, ST st) {
+    const int main_last = len - cutm;
+    if (s0 <= main_last) {
+        pipe_scan_lead<V>(s0, step, main_last, [&](int s) { return ld(s, std::false_type{}); },
+                          [&](const V &v, int s) { st(v, s, std::false_type{}); });
+        s0 += ((main_last - s0) / step + 1) * step;
+    }
+    if (cutm > 0 && s0 <= len)
+        pipe_scan_lead<V>(s0, step, len, [&](int s) { return ld(s, std::true_type{}); },
+                          [&](const V &v, int s) { st(v, s, std::true_type{}); });
 }
 
 
@@ -1564,22 +1582,26 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     // their loads still hit valid cells.
     // ---- split-point sharing roles (ccj_engine.h), wave-uniform: 0 = own full scan, 1 = leader
     // (full scan, also for the next SHARE_R-1 cells of its columns), 2 = follower (scans only the
-    // split points 1..a%R / 1..b%R, takes the rest from its leader's partial record).  A leader's
-    // W(i-r, .) / W(., j+r) operands have spans up to a+r-1 <= t-1 only if b >= r (a-side) / a >= r
-    // (b-side), so columns with a short other gap keep full scans.
+    // split points 1..a%R / 1..b%R and the few top ones its leader had to leave out, takes the rest
+    // from its leader's partial record).  A leader's W(i-r, .) / W(., j+r) operand at split point s
+    // has span s+r-1 <= t-1 only for s <= a+b-r: where the other gap is short (b < r on the a side,
+    // a < r on the b side) the leader masks follower r on its top r-b / r-a points (share_role).
     const bool grp = t >= T.g_lo && t < T.g_hi;
-    const int ra = a % SHARE_R, rb = b % SHARE_R;
-    const int arole = (grp && b >= SHARE_R - 1) ? (ra == 0 ? 1 : (t - ra >= T.g_lo ? 2 : 0)) : 0;
-    const int brole = (grp && a >= SHARE_R - 1) ? (rb == 0 ? 1 : (t - rb >= T.g_lo ? 2 : 0)) : 0;
+    const ShareRole sa = share_role(grp, T.share_edges, a, b, T.g_lo), sb = share_role(grp, T.share_edges, b, a, T.g_lo);
+    const int arole = sa.role, brole = sb.role;
     // On sharing levels every wave with a long scan (a leader, or a full scan on either side) runs
     // in its own launch (k_level4d_lead: more registers, scans split over several waves); the plain
     // kernel keeps the cells that only follow (short scans, full occupancy).
     TL_META((unsigned)a | (unsigned)part << 10 | (unsigned)arole << 13 | (unsigned)brole << 15 | 1u << 20);
     if (grp && LEAD != (arole != 2 || brole != 2)) return;
     TL_META((unsigned)a | (unsigned)part << 10 | (unsigned)arole << 13 | (unsigned)brole << 15);
-    // last split step this cell scans itself
-    const int a_stop = arole == 2 ? ra : a;
-    const int b_stop = brole == 2 ? rb : b;
+    // the split points this cell scans itself, as the steps 1 .. low+top of one scan: 1 .. low,
+    // then (skipping what the leader's partial covers) its top `top` ones, len-top+1 .. len.  The
+    // masked last split point (s = len) is the scan's last step where the scan reaches it
+    const int a_stop = sa.low + sa.top, a_skip = a - a_stop;
+    const int b_stop = sb.low + sb.top, b_skip = b - b_stop;
+    const int a_mlim = (a_skip == 0 || sa.top > 0) ? a_stop : a_stop + 1;
+    const int b_mlim = (b_skip == 0 || sb.top > 0) ? b_stop : b_stop + 1;
 
     // ---- fused a-loop: split point d inside [i, j] ----
     // (the PM / PO multiloop families' split terms, :544-644, are not here: closed forms, ccj_pmpo2d.h)
@@ -1635,7 +1657,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             for (int f = 0; f < LA_J; ++f) AJ_[r][f] = INF;
         }
         struct LA { rec_t wi, wj; int q[SHARE_R], p[SHARE_R]; };  // raw loads of one split step
-        auto ld = [&](int s) {
+        auto ld = [&](int s, auto tail) {
             LA v;
             const LvlDev L = LD[t - s];
             const int Ui = (a - s) * L.M + s;
@@ -1649,7 +1671,8 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             // span-major rows: W(i-r, i+s-1) and W(j-s+1, j+r) have span s-1+r, coalesced along the lanes
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
-                const int o = (s - 1 + r) * rs;
+                // (tail: a span past t-1 belongs to a point this follower is masked on: any finished row)
+                const int o = (decltype(tail)::value ? imin(s - 1 + r, t - 1) : s - 1 + r) * rs;
 #ifdef CCJ_ABLATE_WHOT
                 // timing only: every W operand load on one cache-resident line (wrong results)
                 v.q[r] = WP[(lane & 15) + 0 * (o + i - r)];
@@ -1661,12 +1684,19 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             }
             return v;
         };
-        auto st = [&](const LA &v, int mask) {
+        // follower r takes the split points s < ml[r]: not the last one (d = j / d = i), and not
+        // the top share_cut(r, b) ones, whose W operand level t does not have yet (wave-uniform).
+        // They differ from a only on the tail (lead_scan)
+        int ml[SHARE_R];
+#pragma unroll
+        for (int r = 0; r < SHARE_R; ++r) ml[r] = a - imax(share_cut(r, b) - 1, 0);
+        auto st = [&](const LA &v, int s, auto tail) {
             const int fLi = lo16(v.wi.x), fOi = hi16(v.wi.x);
             const int fLj = lo16(v.wj.x);
             const int fMpj = lo16(v.wj.y), Kj = hi16(v.wj.y);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
+                const int mask = s < (decltype(tail)::value ? ml[r] : a) ? 0 : INF;
                 const int wpi = v.q[r], wpj = v.p[r];
                 int *I = AI_[r], *J = AJ_[r];
                 I[0] = imin(I[0], fLi + wpi + mask);     // PfromL    :357-359
@@ -1676,7 +1706,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                 J[2] = imin(J[2], Kj + wpj + mask);      // PK        :184-187
             }
         };
-        if (1 + part <= a) pipe_scan_lead<LA>(1 + part, split, a, a, ld, st);
+        lead_scan<LA>(1 + part, split, a, share_cut(SHARE_R - 1, b), ld, st);
         // slices handed over through the ring: the followers' (r >= 1); r = 0 stays in this wave's
         // accumulators
         constexpr int r0 = 1;
@@ -1744,9 +1774,9 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     if (arole == 1 && LEAD) {
         lead_a();
     } else if (1 + part <= a_stop) {
-        pipe_scan<AV>(1 + part, split, a_stop, a, load_a, step_a);
+        pipe_scan<AV>(1 + part, split, a_stop, a_mlim, [&](int v) { return load_a(v > sa.low ? v + a_skip : v); }, step_a);
     }
-    // the ring record of the a-loop: a follower's leader partial (split points a%R+1 .. a)
+    // the ring record of the a-loop: a follower's leader partial (split points a%R+1 .. a-top)
     if (arole == 2) {
         const uint2 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;
         const unsigned idx = (unsigned)(a * Mt) + L0;
@@ -1812,7 +1842,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             for (int f = 0; f < LB_L; ++f) AL_[r][f] = INF;
         }
         struct LB { rk_t wk; rl_t wl; int q[SHARE_R], p[SHARE_R]; };  // raw loads of one split step
-        auto ld = [&](int s) {
+        auto ld = [&](int s, auto tail) {
             LB v;
             const LvlDev L = LD[t - s];
             const int Uk = a * L.M + s * m + ((s * (s + 1)) >> 1);
@@ -1826,7 +1856,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             v.wl = lp[(unsigned)Ul + lh];
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
-                const int o = (s - 1 + r) * rs;
+                const int o = (decltype(tail)::value ? imin(s - 1 + r, t - 1) : s - 1 + r) * rs;
 #ifdef CCJ_ABLATE_WHOT
                 v.q[r] = WP[(lane & 15) + 0 * (o + k - r)];
                 v.p[r] = WP[(lane & 15) + 16 + 0 * (o + l - s)];
@@ -1837,11 +1867,15 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
             }
             return v;
         };
-        auto st = [&](const LB &v, int mask) {
+        int ml[SHARE_R];  // as for the a-loop, with the gaps exchanged
+#pragma unroll
+        for (int r = 0; r < SHARE_R; ++r) ml[r] = b - imax(share_cut(r, a) - 1, 0);
+        auto st = [&](const LB &v, int s, auto tail) {
             const int fRk = lo16(v.wk.x), PLRk = hi16(v.wk.x), Kk = lo16(v.wk.y);
             const int fRl = lo16(v.wl), fOl = hi16(v.wl);
 #pragma unroll
             for (int r = 0; r < SHARE_R; ++r) {
+                const int mask = s < (decltype(tail)::value ? ml[r] : b) ? 0 : INF;
                 const int wpk = v.q[r], wpl_ = v.p[r];
                 int *K = AK_[r], *Q = AL_[r];
                 K[0] = imin(K[0], fRk + wpk + mask);        // PfromR    :379-381
@@ -1851,7 +1885,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
                 Q[1] = imin(Q[1], fOl + wpl_ + mask);       // PfromO    :429-431
             }
         };
-        if (1 + part <= b) pipe_scan_lead<LB>(1 + part, split, b, b, ld, st);
+        lead_scan<LB>(1 + part, split, b, share_cut(SHARE_R - 1, a), ld, st);
         constexpr int r0 = 1;
         if (split > 1) {
             int *slot = red + (wib / split) * (split - 1) * LEAD_RED * 64 + lane;
@@ -1917,7 +1951,7 @@ __device__ __forceinline__ void level4d_body(const DevTables &T, int t, int wave
     if (brole == 1 && LEAD) {
         lead_b();
     } else if (1 + part <= b_stop) {
-        pipe_scan<BV>(1 + part, split, b_stop, b, load_b, step_b);
+        pipe_scan<BV>(1 + part, split, b_stop, b_mlim, [&](int v) { return load_b(v > sb.low ? v + b_skip : v); }, step_b);
     }
     if (brole == 2) {  // the b-loop's ring record (as for the a-loop)
         const uint2 *ring = T.acc + (long long)((t % SHARE_SLOTS) * SHARE_NACC) * T.accC;

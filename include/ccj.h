@@ -300,6 +300,15 @@ int  ccj_level_schedule(int n, int t, int world, int rank, int split_target, int
  * out7 = the five values above, then {resolved split_target, share (0/1)}.  rank < 0: the
  * context's own rank; another rank only in a shard_simulate context. */
 int  ccj_ctx_level_schedule(const ccj_ctx *ctx, int t, int rank, int *out7);
+/* The split-point-sharing roles of a-block a (0 .. t) of level t (host helper, no GPU),
+ * from the one role function the level kernels and the leader lists use.  split_target as above;
+ * edges: 1 = columns whose other gap is below 3 share too (the default), 0 = they scan in full
+ * (what CCJ_SHARE_EDGES=0 makes a context do).  out16 = the a-loop's side, then the b-loop's, each
+ *   {role (0 full scan, 1 leader, 2 follower), low, top (the cell scans split points 1 .. low and
+ *    len-top+1 .. len of its range 1 .. len itself), cut of follower r = 1, 2, 3 (a leader leaves its
+ *    top `cut` split points out of that follower's partial; 0 for other roles)},
+ * then {1: k_level4d_lead runs the block, 1: level t shares, g_lo, g_hi}. */
+int  ccj_share_roles(int n, int t, int a, int split_target, int edges, int *out16);
 /* The level-t exchange is two all-gathers: part 0 ("edge") = each rank's blocks
  * a % 4 == 3, the only cells of level t another rank's level t+1 reads, then its P(t+1) partials
  * (4(n+1) elements) and span t (20(n+1) elements), on the level stream; part 1 ("bulk") = the other
