@@ -114,6 +114,109 @@ class _Options(ctypes.Structure):
                 ("shard_rank", ctypes.c_int), ("shard_simulate", ctypes.c_int), ("host_traceback", ctypes.c_int),
                 ("split_target", ctypes.c_int), ("share_splits", ctypes.c_int)]
 
+class _Constraint(ctypes.Structure):
+    """include/ccj.h ccj_constraint"""
+    _fields_ = [("unpaired", ctypes.c_char_p), ("forbid", ctypes.POINTER(ctypes.c_int)), ("n_forbid", ctypes.c_int),
+                ("allow_only", ctypes.POINTER(ctypes.c_int)), ("n_allow", ctypes.c_int)]
+
+
+class Constraint:
+    """Negative folding constraints for one sequence (include/ccj.h ccj_constraint):
+    positions that must stay unpaired and pairs that must not form.  Pairs cannot be forced.
+
+    ``unpaired``: a string of the sequence's length over ``.`` and ``x`` (the ViennaRNA convention);
+    ``x`` at position p forbids every pair of p.  ``forbid``: 1-based pairs (i, j), i < j, that must
+    not form.  ``allow_only``: if given, only the listed pairs may form at all (before the two above
+    are applied).  ``Constraint("..xx..")`` and ``Constraint(forbid=[(2, 9)])`` both work.
+
+    The checks that need no sequence run here (characters, i < j, i >= 1); ``check(n)`` runs the ones
+    that need its length, and every call that takes a constraint does so before it touches a context.
+    All of them raise ``CCJError(CCJ_E_ARG)``, the code the ABI refuses the same defects with."""
+
+    def __init__(self, unpaired: Optional[str] = None, forbid=(), allow_only=None):
+        if unpaired is not None:
+            if not isinstance(unpaired, str):
+                raise CCJError(CCJ_E_ARG, "constraint: the unpaired string must be a str")
+            bad = sorted(set(unpaired) - set(".x"))
+            if bad:
+                raise CCJError(CCJ_E_ARG, f"constraint: unpaired string has characters other than '.' and 'x': {bad}")
+        self.unpaired = unpaired
+        self.forbid = self._pairs(forbid, "forbid")
+        self.allow_only = None if allow_only is None else self._pairs(allow_only, "allow_only")
+
+    @staticmethod
+    def _pairs(pairs, name):
+        out = []
+        for pr in pairs:
+            try:
+                i, j = pr
+                ok = int(i) == i and int(j) == j
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise CCJError(CCJ_E_ARG, f"constraint: {name} entry {pr!r} is not a pair of positions")
+            i, j = int(i), int(j)
+            if i < 1 or i >= j:
+                raise CCJError(CCJ_E_ARG, f"constraint: {name} pair ({i}, {j}) is not 1 <= i < j")
+            out.append((i, j))
+        return tuple(out)
+
+    @classmethod
+    def parse(cls, text: str) -> "Constraint":
+        """The string form: one character per position, ``.`` free, ``x`` unpaired."""
+        return cls(unpaired=text.strip())
+
+    def check(self, n: int) -> "Constraint":
+        """Raise unless the constraint fits a sequence of length n."""
+        if self.unpaired is not None and len(self.unpaired) != n:
+            raise CCJError(CCJ_E_ARG, f"constraint: unpaired string of length {len(self.unpaired)}, sequence of {n}")
+        for name, pairs in (("forbid", self.forbid), ("allow_only", self.allow_only or ())):
+            for i, j in pairs:
+                if j > n:
+                    raise CCJError(CCJ_E_ARG, f"constraint: {name} pair ({i}, {j}) outside 1..{n}")
+        return self
+
+    def forbidden(self, n: int) -> set:
+        """The set F of forbidden position pairs (i, j), i < j, for a sequence of length n."""
+        self.check(n)
+        F = set()
+        if self.allow_only is not None:
+            F = {(i, j) for i in range(1, n + 1) for j in range(i + 1, n + 1)} - set(self.allow_only)
+        if self.unpaired:
+            for p, ch in enumerate(self.unpaired, 1):
+                if ch == "x":
+                    F |= {(min(p, q), max(p, q)) for q in range(1, n + 1) if q != p}
+        return F | set(self.forbid)
+
+    def _c(self):
+        """(the ccj_constraint, the buffers it points into)."""
+        fb = (ctypes.c_int * max(1, 2 * len(self.forbid)))(*[v for pr in self.forbid for v in pr])
+        ao = None
+        if self.allow_only is not None:
+            ao = (ctypes.c_int * max(1, 2 * len(self.allow_only)))(*[v for pr in self.allow_only for v in pr])
+        c = _Constraint(self.unpaired.encode() if self.unpaired is not None else None,
+                        ctypes.cast(fb, ctypes.POINTER(ctypes.c_int)), len(self.forbid),
+                        ctypes.cast(ao, ctypes.POINTER(ctypes.c_int)) if ao is not None else None,
+                        len(self.allow_only) if self.allow_only is not None else 0)
+        return c, (fb, ao)
+
+    def __repr__(self):
+        return f"Constraint(unpaired={self.unpaired!r}, forbid={list(self.forbid)!r}, allow_only=" \
+               f"{None if self.allow_only is None else list(self.allow_only)!r})"
+
+
+def _cons_arg(constraint, n):
+    """A ccj_constraint pointer (or None) for a call, with what must outlive the call."""
+    if constraint is None:
+        return None, None
+    if isinstance(constraint, str):
+        constraint = Constraint.parse(constraint)
+    if not isinstance(constraint, Constraint):
+        raise CCJError(CCJ_E_ARG, "constraint: expected a Constraint, its string form or None")
+    c, keep = constraint.check(n)._c()
+    return ctypes.byref(c), (c, keep)
+
+
 COMM_ID_BYTES = 128
 DEFAULT_SPLIT_TARGET = 9216  # ccj_host.cc create_impl (include/ccj.h ccj_options.split_target)
 
@@ -156,6 +259,20 @@ def lib() -> ctypes.CDLL:
     L.ccj_rebind.restype = ip
     L.ccj_capacity.argtypes = [vp]
     L.ccj_capacity.restype = ip
+    if hasattr(L, "ccj_rebind_constrained"):  # not in a CCJ_LIB_VARIANT built from an older tree (A/B runs)
+        consp = ctypes.POINTER(_Constraint)
+        L.ccj_reset_constrained.argtypes = [vp, cp, consp]
+        L.ccj_reset_constrained.restype = ip
+        L.ccj_rebind_constrained.argtypes = [vp, cp, consp]
+        L.ccj_rebind_constrained.restype = ip
+        L.ccj_batch_bind_constrained.argtypes = [vp, ctypes.POINTER(cp), ctypes.POINTER(consp), ip]
+        L.ccj_batch_bind_constrained.restype = ip
+        L.ccj_constraint_count.argtypes = [vp]
+        L.ccj_constraint_count.restype = ctypes.c_longlong
+        L.ccj_il_prune_host_constrained.argtypes = [ctypes.POINTER(_Problem), consp, ctypes.POINTER(ctypes.c_longlong)] + [vp] * 6
+        L.ccj_il_prune_host_constrained.restype = ip
+        L.ccj_work_model_seq_constrained.argtypes = [cp, ip, consp, ctypes.POINTER(ctypes.c_double)]
+        L.ccj_work_model_seq_constrained.restype = ip
     L.ccj_layout_extents.argtypes = [ip, ip, ip, ip, ip, ctypes.POINTER(ctypes.c_longlong), ip]
     L.ccj_layout_extents.restype = ip
     L.ccj_layout_extent_names.argtypes = []
@@ -337,12 +454,13 @@ IL_U = 29  # ccj_engine.h IE_U: u1, u2 in [0, 28]
 
 
 def il_prune_host(seq: str, params: str | bytes = "Turner04", dangle: int = 2, noGU: bool = False, pen=None,
-                  windows: bool = True):
+                  windows: bool = True, constraint=None):
     """The candidate-list pruning rule on the host, no GPU (include/ccj.h ccj_il_prune_host).
 
     Returns a dict: ``counts`` = (il kept, il full, ilm kept, ilm full) and, with ``windows``, the numpy
     arrays ``e_il``, ``e_ilm`` (int16) and ``st_il``, ``st_ilm`` (uint8), each [w][p][u1][u2] with p in
-    [0, n+2), and the planes ``est``, ``ie`` [w][p]: see the header for the status values."""
+    [0, n+2), and the planes ``est``, ``ie`` [w][p]: see the header for the status values.
+    ``constraint``: the rule under a Constraint (ccj_il_prune_host_constrained)."""
     import numpy as np
     blob = params if isinstance(params, (bytes, bytearray)) else load_params(params)
     blob_buf = ctypes.create_string_buffer(bytes(blob), len(blob))
@@ -362,7 +480,11 @@ def il_prune_host(seq: str, params: str | bytes = "Turner04", dangle: int = 2, n
                                             ("st_ilm", np.uint8, shape), ("est", np.int16, shape[:2]), ("ie", np.int16, shape[:2])]):
             out[name] = np.zeros(sh, dtype=dt)
             ptrs[x] = out[name].ctypes.data_as(ctypes.c_void_p)
-    rc = lib().ccj_il_prune_host(ctypes.byref(prob), counts, *ptrs)
+    consp, _keep = _cons_arg(constraint, len(seq))
+    if consp is None:
+        rc = lib().ccj_il_prune_host(ctypes.byref(prob), counts, *ptrs)
+    else:
+        rc = lib().ccj_il_prune_host_constrained(ctypes.byref(prob), consp, counts, *ptrs)
     if rc != CCJ_OK:
         raise CCJError(rc, "ccj_il_prune_host")
     out["counts"] = tuple(counts)
@@ -451,7 +573,8 @@ class W_final:
                  noGU: bool = False, device: int = 0, overlap_d2h: bool = False, shard_world: int = 1,
                  shard_rank: int = 0, shard_simulate: bool = False, comm_id: Optional[bytes] = None,
                  host_traceback: bool = False, split_target: int = 0, share_splits: int = 0,
-                 local_group: Optional["LocalGroup"] = None, pen=None, capacity: Optional[int] = None):
+                 local_group: Optional["LocalGroup"] = None, pen=None, capacity: Optional[int] = None,
+                 constraint: Optional["Constraint"] = None):
         """shard_world > 1: band-shard this one sequence over shard_world processes (one per GPU),
         exchanging each level over RCCL; every rank passes the same comm_id (from comm_unique_id()
         on one rank), or the same local_group when the ranks are contexts of this process.
@@ -464,7 +587,14 @@ class W_final:
         struct's order: PS PSM PSP PB PUP PPS a b c ap bp cp (ints) e_stP e_intP (floats); None =
         the reference's h_globals.hh defaults (PEN_DEFAULT).
         capacity: allocate for every length 1 .. capacity (include/ccj.h ccj_create_cap), so that
-        rebind() can bind sequences of other lengths; None = the length of seq."""
+        rebind() can bind sequences of other lengths; None = the length of seq.
+        constraint: a Constraint (or its string form) for this binding: positions that must stay
+        unpaired, pairs that must not form (include/ccj.h ccj_rebind_constrained).  A band-sharded fold
+        needs the same constraint on every rank.  The context is created on the unconstrained sequence
+        and then rebound under the constraint (the ABI has no constrained constructor), so a constrained
+        constructor pays the sequence setup, with its wait for the work-item counts, twice; reset() and
+        rebind() with a constraint pay it once."""
+        consp, _keep = _cons_arg(constraint, len(seq))  # a bad constraint is refused before anything is allocated
         self.seq = seq
         self.n = len(seq)
         self.dangle = dangle
@@ -490,6 +620,8 @@ class W_final:
         if rc != CCJ_OK:
             raise CCJError(rc, L.ccj_last_error(None).decode())
         self._h = h
+        if consp is not None:
+            self._check(L.ccj_rebind_constrained(h, seq.encode(), consp))
         if shard_world > 1 and not shard_simulate and local_group is not None:
             self._group = local_group  # keeps the group alive as long as this context
             self._check(L.ccj_comm_init_local(h, local_group._h))
@@ -501,22 +633,31 @@ class W_final:
         self.energy: Optional[float] = None
         self.stdout_msgs = ""
 
-    def reset(self, seq: str) -> None:
+    def reset(self, seq: str, constraint: Optional["Constraint"] = None) -> None:
         """Rebind this context to another sequence of the same length (include/ccj.h ccj_reset):
-        the allocations are reused, only the sequence tables and work lists are rebuilt."""
+        the allocations are reused, only the sequence tables and work lists are rebuilt.  The binding
+        carries `constraint` and nothing of an earlier one (None: an unconstrained fold)."""
         if len(seq) != self.n:
             raise CCJError(CCJ_E_ARG, f"reset: length {len(seq)} differs from n={self.n}")
-        self._check(lib().ccj_reset(self._h, seq.encode()))
+        consp, _keep = _cons_arg(constraint, len(seq))
+        if consp is None:
+            self._check(lib().ccj_reset(self._h, seq.encode()))
+        else:
+            self._check(lib().ccj_reset_constrained(self._h, seq.encode(), consp))
         self.seq = seq
         self._seq_buf = ctypes.create_string_buffer(seq.encode())
         self.structure = None
         self.energy = None
         self.stdout_msgs = ""
 
-    def rebind(self, seq: str) -> None:
+    def rebind(self, seq: str, constraint: Optional["Constraint"] = None) -> None:
         """Bind this context to another sequence of any length up to its capacity (include/ccj.h
         ccj_rebind): nothing is allocated; with the bound length it is reset()."""
-        self._check(lib().ccj_rebind(self._h, seq.encode()))
+        consp, _keep = _cons_arg(constraint, len(seq))
+        if consp is None:
+            self._check(lib().ccj_rebind(self._h, seq.encode()))
+        else:
+            self._check(lib().ccj_rebind_constrained(self._h, seq.encode(), consp))
         self.seq = seq
         self.n = len(seq)
         self._seq_buf = ctypes.create_string_buffer(seq.encode())
@@ -528,6 +669,11 @@ class W_final:
     def capacity(self) -> int:
         """The longest sequence this context can be bound to (ccj_capacity)."""
         return lib().ccj_capacity(self._h)
+
+    def constraint_count(self) -> int:
+        """Pairs the binding's constraint forbids among those whose bases could pair
+        (ccj_constraint_count); 0 for an unconstrained binding."""
+        return lib().ccj_constraint_count(self._h)
 
     def _check(self, rc: int):
         if rc == CCJ_E_RANGE:
@@ -746,10 +892,21 @@ class LockstepBatch:
         if rc != CCJ_OK:
             raise CCJError(rc, lib().ccj_batch_last_error(self._h).decode())
 
-    def bind(self, seqs) -> None:
+    def bind(self, seqs, constraints=None) -> None:
+        """Member k folds seqs[k]; constraints: None, or one entry per sequence, each a Constraint
+        (or its string form) or None (include/ccj.h ccj_batch_bind_constrained)."""
         seqs = [str(s) for s in seqs]
         arr = (ctypes.c_char_p * max(len(seqs), 1))(*[s.encode() for s in seqs])
-        self._check(lib().ccj_batch_bind(self._h, arr, len(seqs)))
+        if constraints is None:
+            self._check(lib().ccj_batch_bind(self._h, arr, len(seqs)))
+        else:
+            constraints = list(constraints)
+            if len(constraints) != len(seqs):
+                raise CCJError(CCJ_E_ARG, f"bind: {len(constraints)} constraints for {len(seqs)} sequences")
+            args = [_cons_arg(c, len(s)) for c, s in zip(constraints, seqs)]  # refused before any member moves
+            carr = (ctypes.POINTER(_Constraint) * max(len(seqs), 1))(
+                *[ctypes.pointer(keep[0]) if keep is not None else None for _, keep in args])
+            self._check(lib().ccj_batch_bind_constrained(self._h, arr, carr, len(seqs)))
         self.count = len(seqs)
         for wf, s in zip(self._all, seqs):
             wf.seq, wf.n = s, len(s)
@@ -916,14 +1073,14 @@ def layout_extents(n: int, split_target: int = DEFAULT_SPLIT_TARGET, share: bool
     return dict(zip(names, out))
 
 
-def _fold_many_lockstep(seqs, k, dangle, params, noGU, device, capacity, pen, engine) -> list:
+def _fold_many_lockstep(seqs, k, dangle, params, noGU, device, capacity, pen, engine, constraints=None) -> list:
     runs = plan_lockstep([len(s) for s in seqs], k)
     cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
     out: list = [None] * len(seqs)
     batch = LockstepBatch(cap, min(max(1, int(k)), len(seqs)), dangle, params=params, noGU=noGU, device=device, pen=pen, **engine)
     try:
         for run in runs:
-            batch.bind([seqs[x] for x in run])
+            batch.bind([seqs[x] for x in run], None if constraints is None else [constraints[x] for x in run])
             batch.fold()
             for x, wf in zip(run, batch.members):
                 if wf.refused is not None:
@@ -938,7 +1095,8 @@ def _fold_many_lockstep(seqs, k, dangle, params, noGU, device, capacity, pen, en
 
 
 def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU: bool = False, device: int = 0,
-              contexts: int = 2, capacity: Optional[int] = None, pen=None, lockstep: int = 0, **engine) -> list:
+              contexts: int = 2, capacity: Optional[int] = None, pen=None, lockstep: int = 0, constraints=None,
+              **engine) -> list:
     """Fold sequences of mixed lengths through `contexts` capacity contexts (capacity: the longest
     sequence by default), kept in flight with rebind + fill_async / wait: while one context's
     traceback runs, the next context's fill has the GPU.  Returns one record per sequence, in input
@@ -948,12 +1106,20 @@ def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU
     its record is (seq, None, None, "", RANGE_EXIT_CODE, message).  engine: further W_final options (split_target, share_splits, host_traceback, ...).
     lockstep=K > 0: instead, sort by length, cut into runs of K neighbours (plan_lockstep) and fold each
     run as one LockstepBatch, which pays every level's launches once per run; the same records, in
-    input order."""
+    input order.
+    constraints: None, or one entry per sequence (a Constraint, its string form, or None), on either
+    path; every entry is checked against its sequence before the first fold starts."""
     seqs = list(seqs)
     if not seqs:
         return []
+    if constraints is not None:
+        constraints = [Constraint.parse(c) if isinstance(c, str) else c for c in constraints]
+        if len(constraints) != len(seqs):
+            raise CCJError(CCJ_E_ARG, f"fold_many: {len(constraints)} constraints for {len(seqs)} sequences")
+        for c, s in zip(constraints, seqs):
+            _cons_arg(c, len(s))
     if lockstep and int(lockstep) > 0:
-        return _fold_many_lockstep(seqs, int(lockstep), dangle, params, noGU, device, capacity, pen, engine)
+        return _fold_many_lockstep(seqs, int(lockstep), dangle, params, noGU, device, capacity, pen, engine, constraints)
     cap = max(len(s) for s in seqs) if capacity is None else int(capacity)
     k = max(1, min(int(contexts), len(seqs)))
     out: list = [None] * len(seqs)
@@ -972,12 +1138,13 @@ def fold_many(seqs, dangle: int = 2, params: str | bytes = "DirksPierce09", noGU
     try:
         for x, s in enumerate(seqs):
             if len(ctx) < k:
-                wf = W_final(s, dangle, params=params, noGU=noGU, device=device, pen=pen, capacity=cap, **engine)
+                wf = W_final(s, dangle, params=params, noGU=noGU, device=device, pen=pen, capacity=cap,
+                             constraint=None if constraints is None else constraints[x], **engine)
                 ctx.append(wf)
             else:
                 wf, done = flying.pop(0)  # the oldest fold in flight: its context is the next free one
                 finish(wf, done)
-                wf.rebind(s)
+                wf.rebind(s, None if constraints is None else constraints[x])
             wf.fill_async()
             flying.append((wf, x))
         while flying:

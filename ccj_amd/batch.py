@@ -1,6 +1,6 @@
 """Fold a file of sequences of mixed lengths through a few capacity contexts (ccj_amd.fold_many).
 
-    python -m ccj_amd.batch [-d N] [-P set] [--noGU] [--contexts K] [--lockstep K] FILE
+    python -m ccj_amd.batch [-d N] [-P set] [--noGU] [--contexts K] [--lockstep K] [--constraints] FILE
 
 FILE holds one sequence per line, or FASTA records (a '>' header line, then the sequence over one
 or more lines); '-' reads standard input.  Sequences are upper-cased and T becomes U, as the CCJ
@@ -11,6 +11,10 @@ character outside GCAU gets the command line's message and counts as exit code 1
 the largest one seen.  -P names a bundled parameter set or a .ccjp / .par path (default
 DirksPierce09).  --lockstep K folds runs of K sequences of neighbouring length as one lockstep batch
 (fold_many(lockstep=K)); the output is the same bytes.  Device: $CCJ_DEVICE, else $LOCAL_RANK, else 0.
+--constraints: a sequence may be followed by one line over '.' and 'x' of its length (in a FASTA record:
+after the sequence's last line); 'x' keeps that position unpaired (ccj_amd.Constraint).  A constraint
+line of another length, or one that follows no sequence, gets a message on stderr, its sequence is not
+folded and counts as exit code 1.  Without the flag the input grammar is unchanged.
 """
 from __future__ import annotations
 
@@ -43,6 +47,50 @@ def read_sequences(lines) -> list:
     return [s.upper().replace("T", "U") for s in seqs]
 
 
+def is_constraint_line(line: str) -> bool:
+    return bool(line) and all(c in ".x" for c in line)
+
+
+def read_records(lines) -> list:
+    """The --constraints grammar: read_sequences' input in which a line over '.' and 'x' belongs to the
+    sequence before it.  Returns (sequence, constraint line or None) pairs; a constraint line that
+    follows no sequence, or a second one, is returned as ("", line)."""
+    recs, cur, fasta = [], None, False   # cur: the open FASTA record [sequence, constraint]
+
+    def attach(line):
+        if recs and recs[-1][0] and recs[-1][1] is None:
+            recs[-1][1] = line
+        else:
+            recs.append(["", line])
+
+    for raw in lines:
+        line = raw.strip()
+        if not line:
+            continue
+        if line.startswith(">"):
+            fasta = True
+            if cur and cur[0]:
+                recs.append(cur)
+            cur = ["", None]
+        elif is_constraint_line(line):
+            if fasta and cur is not None and cur[0] and cur[1] is None:
+                cur[1] = line
+            elif fasta and cur is not None:
+                if cur[0]:
+                    recs.append(cur)
+                    cur = ["", None]
+                recs.append(["", line])
+            else:
+                attach(line)
+        elif fasta:
+            cur[0] += line
+        else:
+            recs.append([line, None])
+    if cur and cur[0]:
+        recs.append(cur)
+    return [(s.upper().replace("T", "U"), c) for s, c in recs]
+
+
 def record_stdout(rec) -> str:
     """What cli.fold_cli returns as stdout for one fold_many record."""
     seq, structure, energy, msgs, code, _ = rec
@@ -60,22 +108,32 @@ def run(argv=None, stdout=None, stderr=None) -> int:
     ap.add_argument("--noGU", action="store_true")
     ap.add_argument("--contexts", type=int, default=2)
     ap.add_argument("--lockstep", type=int, default=0)
+    ap.add_argument("--constraints", action="store_true")
     ap.add_argument("file")
     a = ap.parse_args(argv)
+    reader = read_records if a.constraints else read_sequences
     if a.file == "-":
-        seqs = read_sequences(sys.stdin)
+        seqs = reader(sys.stdin)
     else:
         with open(a.file) as f:
-            seqs = read_sequences(f)
+            seqs = reader(f)
+    cons = [None] * len(seqs)
     bad = {}
+    if a.constraints:
+        seqs, cons = [s for s, _ in seqs], [c for _, c in seqs]
+        for x, (s, c) in enumerate(zip(seqs, cons)):
+            if c is not None and len(c) != len(s):
+                stderr.write(f"Constraint line of length {len(c)} for a sequence of length {len(s)}.\n")
+                bad[x] = ""
     for x, s in enumerate(seqs):
         c = next((c for c in s if c not in "GCAU"), None)
-        if c is not None:
+        if c is not None and x not in bad:
             bad[x] = f"Sequence contains character {c} that is not G,C,A,U, or T.\n"
     good = [s for x, s in enumerate(seqs) if x not in bad]
+    good_cons = [c for x, c in enumerate(cons) if x not in bad] if any(c is not None for c in cons) else None
     device = int(os.environ.get("CCJ_DEVICE", os.environ.get("LOCAL_RANK", "0")))
     recs = iter(fold_many(good, a.dangles, params=load_params(a.paramFile), noGU=a.noGU, device=device,
-                          contexts=a.contexts, lockstep=a.lockstep))
+                          contexts=a.contexts, lockstep=a.lockstep, constraints=good_cons))
     code = 0
     for x in range(len(seqs)):
         if x in bad:

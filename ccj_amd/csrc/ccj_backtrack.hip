@@ -34,7 +34,18 @@ struct DevStore {
     const int8_t *pair, *rtype;
     const LvlDev *ld;
 
-    __device__ __forceinline__ int pr(int i, int j) const { return pair[S[i] * 8 + S[j]]; }
+    // pair[S[i]][S[j]] of the binding's relation.  The table lookup behind the LDS copies is all an
+    // unconstrained binding does (T.cons = 0, uniform); under a constraint a pair type is then checked
+    // against the pt plane, which holds 0 at the constraint's pairs (either order of i, j; a position
+    // outside 1..n is the reference's own S[0] / S[n+1] lookup and stays with the table)
+    __device__ __forceinline__ int pr(int i, int j) const {
+        int t = pair[S[i] * 8 + S[j]];
+        if (T.cons && t > 0) {
+            const int lo = imin(i, j), hi = imax(i, j);
+            if (lo >= 1 && hi <= n && T.pt[(hi - lo) * rs + lo] == 0) t = 0;
+        }
+        return t;
+    }
     __device__ __forceinline__ int rt(int type) const { return rtype[type]; }
     __device__ __forceinline__ const ccj_energy_params *prm() const { return T.prm; }
     __device__ __forceinline__ const int *lx() const { return T.lx; }

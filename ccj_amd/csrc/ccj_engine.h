@@ -266,7 +266,7 @@ struct DevTables {
     const ccj_energy_params *prm;  // device copy of the blob
     const int *lx;                 // (int)(lxc*log(x/30.)), x in [0, 2n+64)
     const short *S, *S1;           // encoded sequence, n+2
-    const int8_t *pt;              // [w][p] pair type pair[S[p]][S[p+w]]
+    const int8_t *pt;              // [w][p] pair type pair[S[p]][S[p+w]], 0 where a constraint forbids (p, p+w): the binding's relation
     const int8_t *pair;            // 8x8 pair table (after noGU)
     const int8_t *rtype;           // 8
     const int *hp;                 // [w][p] HairpinE (s_energy_matrix.cc:275-282), INF if type 0
@@ -315,6 +315,7 @@ struct DevTables {
     long long xspan;               // bytes k_iloop may address from a wave's buffer base (debug check)
     int g_lo, g_hi;
     int share_edges;               // 1: columns with a short other gap share too (share_role; CCJ_SHARE_EDGES=0: 0)
+    int cons;                      // 1: the binding carries a constraint (pt holds 0 at its pairs; the traceback's pr)
     // k_level4d_lead walks only the long-scan a-blocks of a sharing level, longest scan first:
     // rank r's list lord[lord_off[t*G+r] .. lord_off[t*G+r+1]) (device), lord_off_h = the same
     // offsets on the host

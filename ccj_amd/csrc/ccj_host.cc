@@ -218,7 +218,17 @@ struct ccj_ctx {
     int16_t *h4 = nullptr;
     std::vector<int> h2i;     // same 9 arrays
     std::vector<int8_t> hvt;
-    std::vector<int> hpt_h;   // pair type table [w][p] host copy (int)
+    std::vector<int> hpt_h;   // pair type table [w][p] host copy (int): the binding's pair relation
+    // the binding's constraint (include/ccj.h): fmask[i*(n+1)+j] = 1 for (i,j) in F, symmetric; empty:
+    // none.  seq_setup folds it into pt / hpt_h, the one source of the relation for every reader
+    std::vector<uint8_t> fmask;
+    long long fcount = 0;     // ccj_constraint_count
+    // pair[S[i]][S[j]] as the binding sees it, for any positions the reference may index
+    int pair_at(int i, int j) const {
+        if (i >= 1 && i <= j && j <= n) return hpt_h[(size_t)(j - i) * rs + i];
+        if (j >= 1 && j < i && i <= n) return rtype[hpt_h[(size_t)(i - j) * rs + j]];
+        return pair[S[i]][S[j]];  // a position outside the sequence (S[0], S[n+1]): the table itself
+    }
     bool filled = false, mirrored = false, mirrored2d = false;
     bool pending = false;                 // a fill is enqueued and not yet finished (fill_finish)
     // the last fill's range sites (CCJ_RANGE_*) and whether they refuse its result
@@ -344,7 +354,7 @@ struct HostStore {
     const int *W;
 
     explicit HostStore(const ccj_ctx *cc) : c(cc), n(cc->n), S(cc->S.data()), S1(cc->S1.data()), W(cc->W.data()) {}
-    int pr(int i, int j) const { return c->pair[S[i]][S[j]]; }
+    int pr(int i, int j) const { return c->pair_at(i, j); }
     int rt(int type) const { return c->rtype[type]; }
     const ccj_energy_params *prm() const { return &c->prm; }
     const int *lx() const { return c->lx.data(); }
@@ -651,13 +661,20 @@ static int seq_setup(ccj_ctx *c) {
     std::vector<int> hp(plane, INF);
     std::vector<int16_t> est(plane, (int16_t)INTERN_INF);
     c->hpt_h.assign(plane, 0);
+    c->fcount = 0;
     for (int w = 0; w < n; ++w)
         for (int p = 1; p + w <= n; ++p) {
             const size_t x = (size_t)w * c->rs + p;
-            const int tc = c->pair[c->S[p]][c->S[p + w]];
+            int tc = c->pair[c->S[p]][c->S[p + w]];
+            if (!c->fmask.empty() && c->fmask[(size_t)p * (n + 1) + p + w]) {  // (p, p+w) in F
+                c->fcount += tc > 0;
+                tc = 0;
+            }
             pt[x] = (int8_t)tc;
             c->hpt_h[x] = tc;
         }
+    // the device traceback consults pt only where the constraint changed the relation at all
+    c->T.cons = c->fcount > 0 ? 1 : 0;
     // the energy tables, built on the host while the GPU counts the work items (below)
     const char *tab_err = nullptr;
     auto energy_tables = [&]() {
@@ -672,7 +689,7 @@ static int seq_setup(ccj_ctx *c) {
                                                    c->seq.c_str() + p - 1);
                 // get_e_stP, pseudo_loop.cc:828-834 (saturated, see k_precompute_ie)
                 if (q - p >= 2 && p + 1 != q - 1) {
-                    const int t2 = c->pair[c->S[p + 1]][c->S[q - 1]];
+                    const int t2 = pt[(size_t)(w - 2) * c->rs + p + 1];
                     const int e = E_IntLoop(&c->prm, c->lx.data(), 0, 0, tc, c->rtype[t2], c->S1[p + 1], c->S1[q - 1],
                                             c->S1[p], c->S1[q]);
                     const long v = lrint(c->e_stP * e);
@@ -1325,8 +1342,60 @@ extern "C" int ccj_create(const ccj_problem *prob, const ccj_options *opts, ccj_
     return ccj_create_cap(prob, opts, prob && prob->seq ? (int)strlen(prob->seq) : 0, out);
 }
 
-// ccj_reset (same_length) and ccj_rebind: `what` names the call in the messages
-static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char *what, bool from_batch = false) {
+// The set F of a constraint for a sequence of length n (include/ccj.h) as a symmetric byte mask,
+// mask[i*(n+1)+j]; cons == NULL leaves it empty (no constraint).  false: a bad constraint, named in why.
+static bool constraint_mask(const ccj_constraint *cons, int n, std::vector<uint8_t> &mask, std::string &why) {
+    mask.clear();
+    if (!cons) return true;
+    const size_t N = (size_t)n + 1;
+    auto bad_pairs = [&](const int *v, int cnt, const char *name) {
+        if (cnt < 0 || (cnt > 0 && !v)) {
+            why = std::string(name) + ": bad count or missing list";
+            return true;
+        }
+        for (int k = 0; k < cnt; ++k) {
+            const int i = v[2 * k], j = v[2 * k + 1];
+            if (i < 1 || j > n || i >= j) {
+                why = std::string(name) + " pair " + std::to_string(k) + " (" + std::to_string(i) + ", " + std::to_string(j) +
+                      ") is not 1 <= i < j <= " + std::to_string(n);
+                return true;
+            }
+        }
+        return false;
+    };
+    if (bad_pairs(cons->forbid, cons->n_forbid, "forbid") || bad_pairs(cons->allow_only, cons->allow_only ? cons->n_allow : 0, "allow_only"))
+        return false;
+    if (cons->unpaired) {
+        if (strlen(cons->unpaired) != (size_t)n) {
+            why = "unpaired string of length " + std::to_string(strlen(cons->unpaired)) + ", sequence of " + std::to_string(n);
+            return false;
+        }
+        for (const char *q = cons->unpaired; *q; ++q)
+            if (*q != '.' && *q != 'x') {
+                why = "unpaired string has a character other than '.' and 'x'";
+                return false;
+            }
+    }
+    mask.assign(N * N, 0);
+    auto set = [&](int i, int j, uint8_t v) { mask[i * N + j] = mask[j * N + i] = v; };
+    if (cons->allow_only) {
+        for (int i = 1; i <= n; ++i)
+            for (int j = i + 1; j <= n; ++j) set(i, j, 1);
+        for (int k = 0; k < cons->n_allow; ++k) set(cons->allow_only[2 * k], cons->allow_only[2 * k + 1], 0);
+    }
+    if (cons->unpaired)
+        for (int p = 1; p <= n; ++p)
+            if (cons->unpaired[p - 1] == 'x')
+                for (int q = 1; q <= n; ++q)
+                    if (q != p) set(p, q, 1);
+    for (int k = 0; k < cons->n_forbid; ++k) set(cons->forbid[2 * k], cons->forbid[2 * k + 1], 1);
+    return true;
+}
+
+// ccj_reset (same_length) and ccj_rebind: `what` names the call in the messages.  mask: the binding's
+// constraint from constraint_mask (checked by the caller), or NULL for none; it is taken over.
+static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char *what, bool from_batch = false,
+                       std::vector<uint8_t> *mask = nullptr) {
     if (!c || !seq) return CCJ_E_ARG;
     if (c->batch && !from_batch) return set_err(c, CCJ_E_STATE, "%s: the context is a member of a lockstep batch", what);
     const std::string s(seq);
@@ -1351,13 +1420,35 @@ static int rebind_impl(ccj_ctx *c, const char *seq, bool same_length, const char
         if (const int rc = bind_layout(c, len)) return rc;
     }
     c->seq = s;
+    if (mask) c->fmask.swap(*mask);
+    else c->fmask.clear();
     c->W.clear();
     c->res_ready = false;
     return seq_setup(c);
 }
 
+static int rebind_constrained(ccj_ctx *c, const char *seq, const ccj_constraint *cons, bool same_length, const char *what) {
+    if (!c || !seq) return CCJ_E_ARG;
+    std::vector<uint8_t> mask;
+    std::string why;
+    // the constraint is checked against the new sequence's length before anything moves; a length the
+    // context refuses is reported by rebind_impl's own checks
+    const size_t len = strlen(seq);
+    const bool len_ok = len >= 1 && len <= (size_t)c->ncap && !(same_length && (int)len != c->n) && !(c->world > 1 && (int)len != c->n);
+    if (len_ok && !constraint_mask(cons, (int)len, mask, why))
+        return set_err(c, CCJ_E_ARG, "%s: bad constraint: %s", what, why.c_str());
+    return rebind_impl(c, seq, same_length, what, false, cons ? &mask : nullptr);
+}
+
 extern "C" int ccj_reset(ccj_ctx *c, const char *seq) { return rebind_impl(c, seq, true, "ccj_reset"); }
 extern "C" int ccj_rebind(ccj_ctx *c, const char *seq) { return rebind_impl(c, seq, false, "ccj_rebind"); }
+extern "C" int ccj_reset_constrained(ccj_ctx *c, const char *seq, const ccj_constraint *cons) {
+    return rebind_constrained(c, seq, cons, true, "ccj_reset_constrained");
+}
+extern "C" int ccj_rebind_constrained(ccj_ctx *c, const char *seq, const ccj_constraint *cons) {
+    return rebind_constrained(c, seq, cons, false, "ccj_rebind_constrained");
+}
+extern "C" long long ccj_constraint_count(const ccj_ctx *c) { return c ? c->fcount : 0; }
 extern "C" int ccj_capacity(const ccj_ctx *c) { return c ? c->ncap : 0; }
 
 
@@ -2153,8 +2244,9 @@ extern "C" int ccj_last_timing(const ccj_ctx *c, double *fill_ms, double *kernel
 // reads of pseudo_loop.cc:181-644) + can_pair-filtered interior-loop candidates and stack terms
 // (get_P{L,R,M}iloop :682-773; PO's interior branch reads nothing, A-Q5) ; each read is one int16.
 // Writes are 22 int16 per cell.  The 2-D kernel's P recurrence (:166-179) reads 2 int16 per term.
-static int work_model(int n, const short *S, const int (*pairt)[8], double *out) {
-    auto pr = [&](int p, int q) { return pairt[S[p]][S[q]]; };
+// pr(p, q), 1 <= p < q <= n: the binding's pair type
+template <class PR>
+static int work_model(int n, PR pr, double *out) {
     auto can = [&](int p, int q) { return (q - p > TURN) && pr(p, q) > 0; };
     // PL/PR window count for outer (p, p+w): u1 <= min(w,30)-2, u2 <= min(w-u1-6, 28)
     std::vector<int> cntW((size_t)(n + 1) * (n + 2), 0);
@@ -2224,7 +2316,7 @@ static int work_model(int n, const short *S, const int (*pairt)[8], double *out)
 extern "C" int ccj_work_model(const ccj_ctx *c, double *out) {
     if (!c || !out) return CCJ_E_ARG;
     double w[5];
-    const int rc = work_model(c->n, c->S.data(), c->pair, w);
+    const int rc = work_model(c->n, [c](int p, int q) { return c->pair_at(p, q); }, w);
     for (int x = 0; x < 4; ++x) out[x] = w[x];
     return rc;
 }
@@ -2232,15 +2324,18 @@ extern "C" int ccj_work_model(const ccj_ctx *c, double *out) {
 extern "C" int ccj_work_split(const ccj_ctx *c, double *out2) {
     if (!c || !out2) return CCJ_E_ARG;
     double w[5];
-    const int rc = work_model(c->n, c->S.data(), c->pair, w);
+    const int rc = work_model(c->n, [c](int p, int q) { return c->pair_at(p, q); }, w);
     out2[0] = 2.0 * w[4];                    // k_iloop: candidate reads
     out2[1] = w[0] - out2[0];                // k_level4d: everything else (incl. 44 B of stores per cell)
     return rc;
 }
 
-extern "C" int ccj_work_model_seq(const char *seq, int noGU, double *out) {
+extern "C" int ccj_work_model_seq_constrained(const char *seq, int noGU, const ccj_constraint *cons, double *out) {
     if (!seq || !out) return CCJ_E_ARG;
     const int n = (int)strlen(seq);
+    std::vector<uint8_t> mask;
+    std::string why;
+    if (!constraint_mask(cons, n, mask, why)) return CCJ_E_ARG;
     int pairt[8][8];
     for (int x = 0; x < 8; ++x)
         for (int y = 0; y < 8; ++y) pairt[x][y] = BP_PAIR[x][y];
@@ -2248,10 +2343,12 @@ extern "C" int ccj_work_model_seq(const char *seq, int noGU, double *out) {
     std::vector<short> S(n + 2, 0);
     for (int i = 1; i <= n; ++i) S[i] = (short)encode_base(seq[i - 1]);
     double w[5];
-    const int rc = work_model(n, S.data(), pairt, w);
+    const int rc = work_model(
+        n, [&](int p, int q) { return !mask.empty() && mask[(size_t)p * (n + 1) + q] ? 0 : pairt[S[p]][S[q]]; }, w);
     for (int x = 0; x < 4; ++x) out[x] = w[x];
     return rc;
 }
+extern "C" int ccj_work_model_seq(const char *seq, int noGU, double *out) { return ccj_work_model_seq_constrained(seq, noGU, nullptr, out); }
 
 // Kept and full entry counts of the last fill's candidate lists (k_build_il; seg[IL_SEG-1] and
 // seg[0] of every pair that can pair): out4 = il kept, il full, ilm kept, ilm full.
@@ -2284,10 +2381,13 @@ extern "C" int ccj_il_counts(ccj_ctx *c, long long *out4) {
 //   e_il / e_ilm: the window energies (0 outside the list)
 //   st_il / st_ilm: 0 = not in the list, 1 = kept, 1 | 2 * (IL_NEAR | IL_FAR bits) = dropped
 //   est, ie: the two planes the rule reads
-extern "C" int ccj_il_prune_host(const ccj_problem *prob, long long *counts4, int16_t *e_il, int16_t *e_ilm, uint8_t *st_il,
-                                 uint8_t *st_ilm, int16_t *est_out, int16_t *ie_out) {
+extern "C" int ccj_il_prune_host_constrained(const ccj_problem *prob, const ccj_constraint *cons, long long *counts4, int16_t *e_il,
+                                             int16_t *e_ilm, uint8_t *st_il, uint8_t *st_ilm, int16_t *est_out, int16_t *ie_out) {
     if (!prob || !prob->seq || !prob->params) return CCJ_E_ARG;
     const int n = (int)strlen(prob->seq), rs = n + 2;
+    std::vector<uint8_t> mask;
+    std::string why;
+    if (!constraint_mask(cons, n, mask, why)) return CCJ_E_ARG;
     if (n < 1 || prob->params->magic != CCJ_PARAMS_MAGIC || prob->params->size_bytes != sizeof(ccj_energy_params)) return CCJ_E_ARG;
     ccj_pk_penalties pk = CCJ_PK_PENALTIES_DEFAULT;
     if (prob->pen) pk = *prob->pen;
@@ -2307,13 +2407,15 @@ extern "C" int ccj_il_prune_host(const ccj_problem *prob, long long *counts4, in
     std::vector<int16_t> est(plane, (int16_t)INTERN_INF), ie(plane, (int16_t)INTERN_INF);
     const IlHostTables T{n, rs, S.data(), S1.data(), pt.data(), pair, rtype, prob->params, lx.data(), pk.e_intP, est.data(), ie.data()};
     bool bad = false;
+    for (int w = 0; w < n; ++w)  // the binding's relation first: est and ie read the inner pair's type from it
+        for (int p = 1; p + w <= n; ++p)
+            pt[(size_t)w * rs + p] = !mask.empty() && mask[(size_t)p * (n + 1) + p + w] ? 0 : pair[S[p] * 8 + S[p + w]];
     for (int w = 0; w < n; ++w)
         for (int p = 1; p + w <= n; ++p) {
             const int q = p + w;
             const size_t x = (size_t)w * rs + p;
-            pt[x] = pair[S[p] * 8 + S[q]];
             if (q - p >= 2 && p + 1 != q - 1) {  // get_e_stP as seq_setup saturates it
-                const int t2 = pair[S[p + 1] * 8 + S[q - 1]];
+                const int t2 = pt[(size_t)(w - 2) * rs + p + 1];
                 const long v = lrint(pk.e_stP * E_IntLoop(prob->params, lx.data(), 0, 0, pt[x], rtype[t2], S1[p + 1], S1[q - 1], S1[p], S1[q]));
                 if (v < -32768 || (pt[x] > 0 && t2 > 0 && v >= INTERN_INF)) bad = true;
                 est[x] = (int16_t)(v >= INTERN_INF ? INTERN_INF : v);
@@ -2360,6 +2462,11 @@ extern "C" int ccj_il_prune_host(const ccj_problem *prob, long long *counts4, in
     if (est_out) memcpy(est_out, est.data(), plane * sizeof(int16_t));
     if (ie_out) memcpy(ie_out, ie.data(), plane * sizeof(int16_t));
     return CCJ_OK;
+}
+
+extern "C" int ccj_il_prune_host(const ccj_problem *prob, long long *counts4, int16_t *e_il, int16_t *e_ilm, uint8_t *st_il,
+                                 uint8_t *st_ilm, int16_t *est_out, int16_t *ie_out) {
+    return ccj_il_prune_host_constrained(prob, nullptr, counts4, e_il, e_ilm, st_il, st_ilm, est_out, ie_out);
 }
 
 extern "C" int ccj_host_timing(const ccj_ctx *c, double *out3) {
@@ -2828,7 +2935,7 @@ extern "C" int ccj_batch_members(const ccj_batch *b) { return b ? b->K : 0; }
 extern "C" int ccj_batch_count(const ccj_batch *b) { return b ? b->count : 0; }
 extern "C" ccj_ctx *ccj_batch_member(ccj_batch *b, int k) { return b && k >= 0 && k < b->K ? b->m[k] : nullptr; }
 
-extern "C" int ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count) {
+static int batch_bind_impl(ccj_batch *b, const char *const *seqs, const ccj_constraint *const *cons, int count) {
     if (!b || !seqs) return CCJ_E_ARG;
     if (b->pending) return batch_err(b, CCJ_E_STATE, "ccj_batch_bind: a fold is in flight (ccj_batch_wait first)");
     if (count < 1 || count > b->K) return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: count %d outside 1..%d", count, b->K);
@@ -2841,11 +2948,18 @@ extern "C" int ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count) 
             if (!(*q == 'A' || *q == 'C' || *q == 'G' || *q == 'U' || *q == 'T'))
                 return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: invalid character in sequence %d", k);
     }
+    // ... and every constraint
+    std::vector<std::vector<uint8_t>> masks(count);
+    for (int k = 0; k < count && cons; ++k) {
+        std::string why;
+        if (!constraint_mask(cons[k], (int)strlen(seqs[k]), masks[k], why))
+            return batch_err(b, CCJ_E_ARG, "ccj_batch_bind: bad constraint of sequence %d: %s", k, why.c_str());
+    }
     BHIP(b, hipSetDevice(b->device));
     const int prev = b->count;
     b->count = 0;  // unbound until every member is
     for (int k = 0; k < count; ++k)
-        if (const int rc = rebind_impl(b->m[k], seqs[k], false, "ccj_batch_bind", true))
+        if (const int rc = rebind_impl(b->m[k], seqs[k], false, "ccj_batch_bind", true, cons && cons[k] ? &masks[k] : nullptr))
             return batch_err(b, rc, "member %d: %s", k, b->m[k]->err.c_str());
     for (int k = count; k < prev; ++k) b->m[k]->filled = b->m[k]->res_ready = false;  // idle now
     // tables, result pointers and every step's launch arguments, through pinned staging
@@ -2874,6 +2988,11 @@ extern "C" int ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count) 
     for (int k = 0; k < count; ++k) BHIP(b, hipStreamWaitEvent(b->st, b->m[k]->ev_stage, 0));
     b->count = count;
     return CCJ_OK;
+}
+
+extern "C" int ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count) { return batch_bind_impl(b, seqs, nullptr, count); }
+extern "C" int ccj_batch_bind_constrained(ccj_batch *b, const char *const *seqs, const ccj_constraint *const *cons, int count) {
+    return batch_bind_impl(b, seqs, cons, count);
 }
 
 extern "C" int ccj_batch_fold_async(ccj_batch *b) {

@@ -2,7 +2,8 @@
 //
 // A candidate of an interior-loop list may be dropped when the fill takes the same inner value by a
 // route that costs no more: through an intermediate pair (x,y) that lies strictly between the list's
-// own pair and the candidate's pair, can pair, and is stacked on one of the two.  With PL as the
+// own pair and the candidate's pair, can pair under the binding (pt: a pair a constraint forbids cannot),
+// and is stacked on one of the two.  With PL as the
 // example (closing pair (i,j), candidate (d,dp), u1 = d-i-1 >= 1, u2 = j-dp-1 >= 1; every store clamps
 // at 32767 and nowhere else, cl):
 //   E  = e_intP(i,d,dp,j)                    the candidate's own energy,
@@ -42,8 +43,10 @@ template <class TB>
 CCJ_HD int il_eint_raw(const TB &T, int u1, int u2, int p, int q) {
     const int d = p + u1 + 1, dp = q - u2 - 1;
     if (dp - d < 1) return INTERN_INF;
-    const int t1 = T.pair[T.S[p] * 8 + T.S[q]];
-    const int t2 = T.pair[T.S[d] * 8 + T.S[dp]];
+    // the binding's relation (the pt plane), not the 8x8 table: under a constraint a forbidden pair is
+    // no pair, so a witness through one is no witness (1 <= p < q <= n and p < d < dp < q here)
+    const int t1 = T.pt[(q - p) * T.rs + p];
+    const int t2 = T.pt[(dp - d) * T.rs + d];
     if (t1 <= 0 || t2 <= 0) return INTERN_INF;
     const int e = E_IntLoop(T.prm, T.lx, u1, u2, t1, T.rtype[t2], T.S1[p + 1], T.S1[q - 1], T.S1[d - 1], T.S1[dp + 1]);
     return (int)rint(T.e_intP * (double)e);

@@ -135,7 +135,7 @@ __device__ int E_MLStem_d(const DevTables &T, int vij, int vi1j, int vij1, int v
     const short *S = T.S;
     const int n = T.n;
     int e = INF, en;
-    int type = T.pair[S[i] * 8 + S[j]];
+    int type = ptype(T, i, j);  // stem types: the binding's relation (pt), so a constraint reaches them
     en = vij;
     if (en != INF) {
         if (T.dangles == 2) en += E_MLstem(P, type, i > 1 ? S[i - 1] : -1, j < n ? S[j + 1] : -1);
@@ -145,11 +145,11 @@ __device__ int E_MLStem_d(const DevTables &T, int vij, int vi1j, int vij1, int v
     if (T.dangles == 1) {
         const int mm5 = S[i], mm3 = S[j];
         en = (j - i - 1 > TURN) ? vi1j : INF;
-        if (en != INF) { en += P->MLbase + E_MLstem(P, T.pair[S[i + 1] * 8 + S[j]], mm5, -1); e = imin(e, en); }
+        if (en != INF) { en += P->MLbase + E_MLstem(P, ptype(T, i + 1, j), mm5, -1); e = imin(e, en); }
         en = (j - 1 - i > TURN) ? vij1 : INF;
-        if (en != INF) { en += P->MLbase + E_MLstem(P, T.pair[S[i] * 8 + S[j - 1]], -1, mm3); e = imin(e, en); }
+        if (en != INF) { en += P->MLbase + E_MLstem(P, ptype(T, i, j - 1), -1, mm3); e = imin(e, en); }
         en = (j - 1 - i - 1 > TURN) ? vi1j1 : INF;
-        if (en != INF) { en += 2 * P->MLbase + E_MLstem(P, T.pair[S[i + 1] * 8 + S[j - 1]], mm5, mm3); e = imin(e, en); }
+        if (en != INF) { en += 2 * P->MLbase + E_MLstem(P, ptype(T, i + 1, j - 1), mm5, mm3); e = imin(e, en); }
     }
     return e;
 }
@@ -159,7 +159,7 @@ __device__ int E_MbLoop_d(const DevTables &T, int WM2ij, int WM2ip1j, int WM2ijm
     const ccj_energy_params *P = T.prm;
     const short *S = T.S;
     int e = INF, en;
-    const int tt = T.pair[S[j] * 8 + S[i]];
+    const int tt = T.rtype[ptype(T, i, j)];  // pair[S[j]][S[i]] of the binding's relation
     switch (T.dangles) {
         case 2:
             e = WM2ij;
@@ -231,7 +231,7 @@ __device__ __forceinline__ int e_intP(const DevTables &T, int u1, int u2, int p,
     const int d = p + u1 + 1, dp = q - u2 - 1;
     if (dp - d < 1) return INTERN_INF;
     // the reference only visits candidates with can_pair() on both pairs
-    if (T.pair[T.S[p] * 8 + T.S[q]] <= 0 || T.pair[T.S[d] * 8 + T.S[dp]] <= 0) return INTERN_INF;
+    if (ptype(T, p, q) <= 0 || ptype(T, d, dp) <= 0) return INTERN_INF;
     const int v = il_eint_raw(T, u1, u2, p, q);  // ccj_ilprune.h: shared with the pruning rule
     if (!il_e_in_range(v)) atomicOr(T.err, 1);
     return v;

@@ -150,6 +150,43 @@ int  ccj_reset(ccj_ctx *ctx, const char *seq);
 int  ccj_create_cap(const ccj_problem *prob, const ccj_options *opts, int nmax, ccj_ctx **out);
 int  ccj_rebind(ccj_ctx *ctx, const char *seq);
 int  ccj_capacity(const ccj_ctx *ctx);
+
+/* ---- constrained folding: forbidden pairs and unpaired positions ----
+ * A constraint belongs to one binding of a sequence of length n.  It defines a symmetric set F of
+ * position pairs (i, j), 1 <= i < j <= n:
+ *   allow_only (non-NULL): F starts as the complement of the listed pairs (NULL: empty);
+ *   unpaired: NULL, or a string of length n over '.' and 'x'; 'x' at position p adds (p, q) for every q;
+ *   forbid: adds its pairs.
+ * Pair lists hold 1-based positions, pair k = (list[2k], list[2k+1]) with list[2k] < list[2k+1].
+ * A constrained fold is the reference's fill, W, traceback and emission with one change: every lookup
+ * pair[S[i]][S[j]] at positions (i, j) gives 0 where (i, j) is in F.  The energy functions, penalties,
+ * noGU, the int16 store and the CCJ_E_RANGE domain stay; a pair that could not pair anyway changes
+ * nothing; an empty F is the unconstrained fold, and F = every G-U position pair with noGU = 0 is the
+ * reference's --noGU run.  Pairs cannot be forced, and the partition function (ccj_pf.h) takes no
+ * constraint.
+ *   ccj_reset_constrained / ccj_rebind_constrained: ccj_reset / ccj_rebind with the constraint `cons`
+ *     (NULL: none).  A constrained fold from the start is ccj_create_cap + ccj_rebind_constrained.
+ *   ccj_batch_bind_constrained: ccj_batch_bind where member k folds seqs[k] under cons[k]; cons, or any
+ *     of its entries, may be NULL.
+ *   The plain ccj_reset, ccj_rebind and ccj_batch_bind bind without a constraint, so a context never
+ *   carries a stale one.
+ * A bad constraint (an unpaired string of another length or with another character, a pair with
+ * i >= j or a position outside 1..n, a negative count, a forbid count without its list) is refused with
+ * CCJ_E_ARG before the context or any batch member is touched: the previous binding still folds.
+ *   ccj_constraint_count: |F| over the pairs (i, j) whose bases could pair under the binding's table
+ *     (after noGU), whatever their distance; 0 for an unconstrained binding and for NULL.
+ * Band-sharded contexts: every rank must be given the same constraint (over RCCL this is the caller's
+ * duty and unverified, like the rest of that path). */
+typedef struct ccj_constraint {
+    const char *unpaired;   /* NULL, or length n over '.' / 'x' */
+    const int *forbid;      /* 2 * n_forbid positions */
+    int n_forbid;
+    const int *allow_only;  /* NULL: no allow-only list; else 2 * n_allow positions (n_allow may be 0) */
+    int n_allow;
+} ccj_constraint;
+int  ccj_reset_constrained(ccj_ctx *ctx, const char *seq, const ccj_constraint *cons);
+int  ccj_rebind_constrained(ccj_ctx *ctx, const char *seq, const ccj_constraint *cons);
+long long ccj_constraint_count(const ccj_ctx *ctx);
 /* Element counts of every device buffer whose size depends on n (host helper, no GPU), in the order
  * of ccj_layout_extent_names() (space separated):
  *   d4 (int16; 6 per cell, 22 with full4), rec, rk, rl (one 8 / 8 / 4-byte record per cell), acc
@@ -227,6 +264,8 @@ int  ccj_wait(ccj_ctx *ctx, char *structure, double *energy_kcal, char *stdout_m
 typedef struct ccj_batch ccj_batch;
 int  ccj_batch_create(const ccj_problem *p, const ccj_options *o, int nmax, int members, ccj_batch **out);
 int  ccj_batch_bind(ccj_batch *b, const char *const *seqs, int count);
+/* member k folds seqs[k] under cons[k] (constrained folding above; cons or cons[k] may be NULL) */
+int  ccj_batch_bind_constrained(ccj_batch *b, const char *const *seqs, const ccj_constraint *const *cons, int count);
 int  ccj_batch_fold_async(ccj_batch *b);
 int  ccj_batch_wait(ccj_batch *b);
 ccj_ctx *ccj_batch_member(ccj_batch *b, int k);
@@ -379,6 +418,12 @@ int  ccj_pmpo2d_low_brute(int n, const int *wbp, int bp, int cp, int valid_only,
 int  ccj_il_counts(ccj_ctx *ctx, long long *out4);
 int  ccj_il_prune_host(const ccj_problem *prob, long long *counts4, int16_t *e_il, int16_t *e_ilm, uint8_t *st_il,
                        uint8_t *st_ilm, int16_t *est, int16_t *ie);
+/* The same under a constraint (NULL: none; CCJ_E_ARG for a bad one): every pair the rule uses, the
+ * intermediate stacked pair of a witness included, is one that can pair under the binding. */
+int  ccj_il_prune_host_constrained(const ccj_problem *prob, const ccj_constraint *cons, long long *counts4, int16_t *e_il,
+                                   int16_t *e_ilm, uint8_t *st_il, uint8_t *st_ilm, int16_t *est, int16_t *ie);
+/* ccj_work_model_seq under a constraint (NULL: none; CCJ_E_ARG for a bad one). */
+int  ccj_work_model_seq_constrained(const char *seq, int noGU, const ccj_constraint *cons, double *out4);
 
 #ifdef __cplusplus
 }
